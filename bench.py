@@ -9,12 +9,20 @@ reference superpixel SAD sweep, the per-pixel NCC 5x5 sweep over 128
 hypotheses x 4 neighbours and its winner-take-all + confidence.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--cost ncc|sad]
+                    [--dump-outputs DIR] [--full]
 
 `value` is the fused step (mvs_ncc_wta_d: the sweep kernel folds the WTA in,
 no cost volume in HBM), on one HIP stream (--concurrent: the superpixel chain
-on a side stream; `concurrent_variant` times that form too).  The same invocation also times the two-pass step
-(materialised [D][H][W] volume + the k_wta streaming pass, bit-identical maps):
-`roofline` is k_wta's HBM read of that volume, the north star's roofline.
+on a side stream).  A plain run sets up, warms up, times the K steps and prints
+the line; --dump-outputs DIR also writes the last timed step's maps as
+DIR/<name>.npy (seeded inputs: two builds can be compared array for array).
+
+--full adds every other leg to the same line: `concurrent_variant` (the side
+stream form), the two-pass step (materialised [D][H][W] volume + the k_wta
+streaming pass, bit-identical maps; `roofline` is k_wta's HBM read of that
+volume, the north star's roofline), the PCIe-inclusive rate, the reference's
+cost and defaults, C3, the C4 view-sharded line and the CPU baseline with the
+depth L1 against the oracle.  The --no-* options trim those legs.
 
 N>1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) the
 ranks come from the environment; `--gpus N` without WORLD_SIZE spawns the N
@@ -83,6 +91,13 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--cost", default=None, choices=["ncc", "sad", "none"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: stream / two-pass variants, k_wta roofline, PCIe "
+                         "rate, reference cost and defaults, C3, the C4 view-sharded line, CPU baseline + depth L1 "
+                         "against the oracle (the --no-* options below trim them; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output arrays as DIR/<name>.npy (float32; integer maps float64; "
+                         "an array above DUMP_MAX_ELEMS elements as a fixed seeded sample of its elements)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sharded", action="store_true", help="skip the C4 view-sharded strong-scaling line")
     ap.add_argument("--no-reference-cost", action="store_true", help="skip the C2 --cost sad sub-line")
@@ -253,6 +268,36 @@ def dry_run(args, world, rank):
                           "dry_run": True, "gather_ok": ok, "world_size": world}), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 1 << 19  # per array: 8 arrays of float64 are 32 MiB, within 64 MB in all
+DUMP_SEED = 0x0D0C
+
+
+def dump_outputs(out, path):
+    """The tensors a caller of the timed step receives (the fields of its
+    output object), one DIR/<name>.npy each: float32, integer maps as float64.
+    An array of more than DUMP_MAX_ELEMS elements is written as the elements at
+    DUMP_MAX_ELEMS flat indices drawn once from a fixed seed (sorted, the same
+    for every run of the same shape), gathered on the device."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    fields = out if isinstance(out, dict) else vars(out)
+    done = {}
+    for name, t in sorted(fields.items()):
+        if not isinstance(t, torch.Tensor):
+            continue
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        sampled = n > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else np.float64)
+        np.save(os.path.join(path, name + ".npy"), a if sampled else a.reshape(tuple(t.shape)))
+        done[name] = {"shape": list(t.shape), "dtype": str(a.dtype), "sampled_elems": DUMP_MAX_ELEMS if sampled else None}
+    return done
 
 
 def _cpu_info():
@@ -437,12 +482,14 @@ def bench(args, world, rank, local):
         kviews = calls["fused_views"] - views0  # the views those launches swept (warmup + timed steps)
         e.set_kernel_timing(False)
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    full = bool(args.full)  # every leg below the headline pass runs under --full only
     units = V if sharded else world * V  # reference views processed per step, whole job
     mpix = units * W * H * args.steps / elapsed / 1e6
     head_timers = {k: list(v) for k, v in timers.items()}
     form_timers = head_timers  # the headline's own form (side stream included): roofline_headline
     serial = None
-    if conc_head:
+    if conc_head and full:
         # the same step on one stream: the fused kernel's own time for
         # roofline_sweep (beside the side stream it shares the CUs)
         _, ser_step = make(fused, False)
@@ -461,7 +508,7 @@ def bench(args, world, rank, local):
                       for f in ("disp", "conf") if getattr(out, f, None) is not None))}
 
     conc_var = None
-    if not conc_head and fused and not sharded and cost == "ncc" and world == 1:
+    if full and not conc_head and fused and not sharded and cost == "ncc" and world == 1:
         _, conc_step = make(fused, True)
         saved = {k: list(v) for k, v in timers.items()}
         c_el, c_out = timed(conc_step, args.steps, max(1, args.warmup), dev, world, sync)
@@ -500,7 +547,10 @@ def bench(args, world, rank, local):
                                    f"view-stack per GPU x{world}"),
                    "refinement": bool(cfg.get("refine")), "consistency_filter": bool(cfg.get("filt")),
                    "streams": "superpixel chain on a side stream" if conc_head else "one"},
+        "full": full,
     }
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if serial is not None:
         res["serial_variant"] = serial
     if conc_var is not None:
@@ -517,7 +567,8 @@ def bench(args, world, rank, local):
             "avg_ms_per_view": round(t_f * 1e3 / vpc, 4),
             "view_cells_per_s": round(cells * nbr * vpc / t_f / 1e9, 3), "unit_view_cells": "G view-cells/s",
             "timing": "HIP events around each mvs_ncc_wta_range_d call of the timed steps, on its stream" +
-                      (" (the serial_variant pass: one stream, the kernel alone on the GPU)" if conc_head else "")}
+                      (" (the serial_variant pass: one stream, the kernel alone on the GPU)" if serial is not None
+                       else "")}
         if ktimes and kviews > 0 and not conc_head:
             res["roofline_sweep"]["kernel_avg_ms_per_view"] = round(sum(ktimes) / kviews, 4)
             res["roofline_sweep"]["kernel_timing"] = ("start / stop events of each fused launch's own dispatch "
@@ -572,7 +623,7 @@ def bench(args, world, rank, local):
                               "pipe_busy_frac": round(mf * 16.0 * v_h / t_h / (1024 * 2.4e9), 4),
                               "basis": "16 matrix-core cycles per v_mfma_i32_16x16x64_i8 on its SIMD, 1024 SIMDs x "
                                        "2.4 GHz"}
-            if conc_head:
+            if serial is not None:
                 rh["serial_form"] = {"avg_ms_per_view": round(t_f * 1e3 / vpc, 4),
                                      "frac": round(valu * vpc / t_f / VALU_PEAK, 4)}
             if per_view.get("stale"):
@@ -583,7 +634,7 @@ def bench(args, world, rank, local):
     # north star's roofline is k_wta's read of that volume
     if cost == "ncc":
         tp_out = out
-        if fused:
+        if fused and full:
             _, tp_step = make(False, False)
             for k in timers:
                 timers[k].clear()
@@ -621,7 +672,7 @@ def bench(args, world, rank, local):
 
     # PCIe-inclusive rate: the RGBx stack H2D from pinned host memory and the
     # disparity maps D2H inside the timed region (never `value`)
-    if not sharded and world == 1 and hasattr(out, "disp"):
+    if full and not sharded and world == 1 and hasattr(out, "disp"):
         host_in = torch.from_numpy(stack).pin_memory()
         src = out.disp_refined if out.disp is None else out.disp
         host_out = torch.empty(tuple(src.shape), dtype=torch.float32).pin_memory()
@@ -642,13 +693,13 @@ def bench(args, world, rank, local):
     # the reference's own arithmetic (SAD over Lab, clcode.cl:1030-1053) on the
     # headline shape: the only cost against which the north star's L1 target
     # is defined (C2 with --cost sad, 3 steps)
-    if args.config == "c2" and cost == "ncc" and world == 1 and not args.no_reference_cost:
+    if full and args.config == "c2" and cost == "ncc" and world == 1 and not args.no_reference_cost:
         res["reference_cost"] = reference_cost(args, e, st, stack, rgbx, cfg, world, sync,
                                                check=rank == 0 and not args.no_cpu_baseline)
 
     # the reference's own algorithm at its own defaults (clMVDE.cpp:14-36), so a
     # regression of its kernels (k_propagate above all) shows in the driver's line
-    if args.config == "c2" and cost == "ncc" and world == 1 and not args.no_reference_defaults:
+    if full and args.config == "c2" and cost == "ncc" and world == 1 and not args.no_reference_defaults:
         try:
             res["reference_defaults"] = reference_defaults(args, e, world, sync,
                                                            check=rank == 0 and not args.no_cpu_baseline)
@@ -657,17 +708,17 @@ def bench(args, world, rank, local):
 
     # BASELINE config 3 (C2 + refinement + consistency filter) inside the default
     # line, its refined and filtered maps against the oracle's full-size run
-    if args.config == "c2" and cost == "ncc" and world == 1 and not args.no_c3:
+    if full and args.config == "c2" and cost == "ncc" and world == 1 and not args.no_c3:
         try:
             res["c3"] = c3_subline(args, e, world, sync, check=rank == 0 and not args.no_cpu_baseline)
         except Exception as ex:  # report, never hide; the headline stands
             res["c3"] = {"error": repr(ex)}
 
     # C4: one 32-view array sharded by reference view over the N GPUs (strong scaling)
-    if not args.no_sharded and args.config in ("c2",) and cost == "ncc":
+    if full and not args.no_sharded and args.config in ("c2",) and cost == "ncc":
         res["view_sharded"] = _guarded_view_sharded(args, e, world, rank, sync, res)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             if sharded:
                 res["cpu_baseline"], res["depth_l1_vs_oracle"] = cpu_baseline_sharded_crop(e, cfg)

@@ -143,7 +143,7 @@ class Pipeline:
     joins the side stream before refinement.  One stream is the default here
     and in bench.py (round 5: with the matrix-core sweep the side stream
     measured no gain); `bench.py --concurrent` runs the headline
-    with it, and the default line reports it as `concurrent_variant`."""
+    with it, and `bench.py --full` reports it as `concurrent_variant`."""
 
     def __init__(self, engine: Engine, settings: params.Settings, W: int, H: int,
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",

@@ -20,7 +20,7 @@ for r in $(seq ${ROUNDS:-2}); do
   for spec in $TAGS; do
     t=${spec%%=*}; lib=$t; ex=""
     if [ "$spec" != "$t" ]; then rest=${spec#*=}; lib=${rest%%/*}; ex=${rest#*/}; fi
-    env $ex MVS_LIB=$PWD/ab/libmvs_$lib.so timeout -k 10 300 python3 bench.py --config ${CONFIG:-c2} --no-cpu-baseline \
+    env $ex MVS_LIB=$PWD/ab/libmvs_$lib.so timeout -k 10 300 python3 bench.py --full --config ${CONFIG:-c2} --no-cpu-baseline \
       --no-sharded --no-reference-cost ${ARGS:-} > gpurun_out/ab_$t.json 2> gpurun_out/ab_$t.err || { tail -3 gpurun_out/ab_$t.err; exit 1; }
     python3 -c "import json;j=json.load(open('gpurun_out/ab_$t.json'));rs=j.get('roofline_sweep',{});print('$t', 'ms/step', j['ms_per_step'], 'Mpix/s', j['value'], 'sweep ms/view', rs.get('avg_ms_per_view'), 'two-pass', j.get('two_pass_variant',{}).get('ms_per_step'))"
   done

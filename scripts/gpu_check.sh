@@ -11,6 +11,8 @@ rc=$?
 echo "pytest rc=$rc"; tail -40 gpurun_out/gpu_tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 if [ "${SKIP_BENCH:-0}" = "1" ]; then exit $rc; fi
+# every leg of the line (variants, sub-lines, CPU baseline), not the headline alone
+BENCH_ARGS=${BENCH_ARGS:---full --steps 5 --warmup 2}
 timeout -k 10 ${BENCH_TIMEOUT:-420} python bench.py ${BENCH_ARGS:---steps 5 --warmup 2} > gpurun_out/bench.json 2> gpurun_out/bench.err
 brc=$?
 echo "bench rc=$brc"; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err

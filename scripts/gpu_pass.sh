@@ -6,8 +6,8 @@
 #   tests            the -m gpu suite                       -> gpurun_out/TAG/gpu_tests.log
 #   tests:EXPR       the -m gpu suite, -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command (bench.py --gpus 1 --steps 20 --warmup 5) -> bench.json
-#   bench:CFG        bench.py --config CFG --no-cpu-baseline  -> bench_CFG.json
+#   bench            the driver's command with every leg (bench.py --full --gpus 1 --steps 20 --warmup 5) -> bench.json
+#   bench:CFG        bench.py --full --config CFG --no-cpu-baseline  -> bench_CFG.json
 #   ab:CFG           interleaved A/B (ab/libmvs_A.so vs the in-tree build), 2 rounds -> ab_CFG.txt
 #   abenv:CFG:VAR=V  interleaved A/B of one environment setting (A: unset, B: VAR=V), 2 rounds
 #   trace:CFG        rocprofv3 --kernel-trace --stats of bench.py --config CFG --steps 5
@@ -29,12 +29,12 @@ for s in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err \
+      timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err \
         || fail bench $O/bench.err
       python3 scripts/bench_brief.py $O/bench.json ;;
     bench:*)
       C=${s#bench:}
-      timeout -k 10 600 python3 bench.py --config $C --no-cpu-baseline --no-sharded > $O/bench_$C.json \
+      timeout -k 10 600 python3 bench.py --full --config $C --no-cpu-baseline --no-sharded > $O/bench_$C.json \
         2> $O/bench_$C.err || fail "$s" $O/bench_$C.err
       python3 scripts/bench_brief.py $O/bench_$C.json ;;
     ab:*)
@@ -64,7 +64,7 @@ for s in "$@"; do
     trace:*)
       C=${s#trace:}
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_$C -o run -- python3 bench.py --config $C \
-        --steps 5 --warmup 2 --no-cpu-baseline --no-sharded --no-reference-cost --no-reference-defaults --no-c3 \
+        --full --steps 5 --warmup 2 --no-cpu-baseline --no-sharded --no-reference-cost --no-reference-defaults --no-c3 \
         > $O/trace_$C.json 2> $O/trace_$C.err || fail "$s" $O/trace_$C.err
       python3 scripts/kstats.py $O/trace_$C > $O/trace_$C.txt 2>&1; head -12 $O/trace_$C.txt ;;
     pmc:*)

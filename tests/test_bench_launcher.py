@@ -151,3 +151,43 @@ def test_committed_pmc_feeds_roofline_headline(config):
     got = bench._valu_insts_fused_per_view(config, cfg["W"], cfg["H"], cfg["dmax"] - cfg["dmin"] + 1)
     assert got is not None and got["insts"] > 0
     assert os.path.exists(os.path.join(root, got["source"]))
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """Every leg beside the headline sits behind --full (off by default);
+    --dump-outputs takes the directory of the dumped arrays."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_is_a_fixed_seeded_sample(tmp_path):
+    """dump_outputs writes every tensor of the step's output as <name>.npy in
+    float32 (integer maps float64): small arrays whole, an array above
+    DUMP_MAX_ELEMS as the same seeded flat sample on every call, and the worst
+    case (8 fields, all sampled, float64) stays below 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 12345
+    g = torch.Generator().manual_seed(1)
+    out = {"disp": torch.rand((3, 5, 7), generator=g), "labels": torch.arange(35, dtype=torch.int32).reshape(5, 7),
+           "big": torch.rand(n, generator=g), "none": None}
+    a, b = tmp_path / "a", tmp_path / "b"
+    done = bench.dump_outputs(out, str(a))
+    bench.dump_outputs(out, str(b))
+    assert sorted(done) == ["big", "disp", "labels"] and sorted(p.name for p in a.iterdir()) == \
+        ["big.npy", "disp.npy", "labels.npy"]
+    disp, labels, big = (np.load(a / f"{k}.npy") for k in ("disp", "labels", "big"))
+    assert disp.dtype == np.float32 and np.array_equal(disp, out["disp"].numpy())
+    assert labels.dtype == np.float64 and np.array_equal(labels, out["labels"].numpy())
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, size=bench.DUMP_MAX_ELEMS, dtype=np.int64))
+    assert big.dtype == np.float32 and np.array_equal(big, out["big"].numpy()[idx])
+    assert done["big"]["sampled_elems"] == bench.DUMP_MAX_ELEMS and done["disp"]["sampled_elems"] is None
+    for k in ("disp", "labels", "big"):
+        assert np.array_equal(np.load(a / f"{k}.npy"), np.load(b / f"{k}.npy"))
+    assert 8 * (8 * bench.DUMP_MAX_ELEMS + 128) < 64e6
