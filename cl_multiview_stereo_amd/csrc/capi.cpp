@@ -153,7 +153,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.7 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.8 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -364,6 +364,13 @@ int mvs_ncc_last_variant_n(mvs_ctx* c, int32_t* out, int cap) {
   const int k = cap < 8 ? cap : 8;
   for (int i = 0; i < k; i++) out[i] = c->ncc_last[i];
   return 8;
+}
+
+int mvs_sweep_last_variant_n(mvs_ctx* c, int32_t* out, int cap) {
+  if (!c || (cap > 0 && !out) || cap < 0) return mvs::arg_fail("mvs_sweep_last_variant_n: bad arguments");
+  const int k = cap < 5 ? cap : 5;
+  for (int i = 0; i < k; i++) out[i] = c->sweep_last[i];
+  return 5;
 }
 
 int mvs_ncc_volume_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,

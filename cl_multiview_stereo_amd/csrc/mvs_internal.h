@@ -35,6 +35,9 @@ struct mvs_ctx {
   // variant of the last launch {K, TH, DPW, NW, BW, PAR, FUSE, NB} (DPW 16: the matrix-core form)
   int ncc_nw = 0, ncc_dpw = 0, ncc_bw = 0, ncc_general = 0;
   int ncc_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // the superpixel sweep's last launch {FORM, LPS, WPS, TMODE, RELAID}
+  // (mvs_sweep_last_variant_n; FORM 0 general, 1 HZ gathers, 2 HZ ring, 3 re-laid)
+  int sweep_last[5] = {0, 0, 0, 0, 0};
   // kernel timing (mvs_set_kernel_timing): the fused NCC sweep's launches carry
   // start / stop events of their own dispatch (hipExtLaunchKernel), pooled
   bool ktime = false;

@@ -1098,9 +1098,11 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
   const long tstride = H;
   const char* te = getenv("MVS_SWEEP_TRANSPOSE");
   const int tmode = te ? atoi(te) : 2;
+  int relaid = 0;  // (view, kind) copies built (the report of mvs_sweep_last_variant_n)
   if (tmode > 0) {
     std::vector<int32_t> slot(4 * (size_t)V, -1);
     long units = 0;
+    int nslots = 0;
     for (int z = z0; z < z1; z++)
       for (int k = 0; k < ctx->h_sn[z]; k++) {
         const int v = ctx->h_vs[(size_t)V * z + k];
@@ -1110,6 +1112,7 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
         if (kind && slot[4 * v + kind] < 0 && units + W + H <= INT32_MAX) {
           slot[4 * v + kind] = (int32_t)units;
           units += kind == 1 ? W : W + H - 1;
+          nslots++;
         }
       }
     if (units > 0) {
@@ -1137,7 +1140,10 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
             hipLaunchKernelGGL(k_relayout_lab<3>, tg, dim3(256), 0, s, (const float4*)lab, W, H, v, o);
         }
       MVS_LAUNCH_CHECK("k_relayout_lab");
-      if (units > 0) labT = buf;
+      if (units > 0) {
+        labT = buf;
+        relaid = nslots;
+      }
     }
   }
   // HZ: every neighbour of [z0, z1) in the reference's camera row and every
@@ -1188,6 +1194,8 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
     else
       hipLaunchKernelGGL(k_sweep_spixl_ring<4>, g, dim3(256), 0, s, (const float4*)lab, spixl, rep, levels, vs, sn, a);
     MVS_LAUNCH_CHECK("k_sweep_spixl_ring");
+    const int last[5] = {2, 64, rw, tmode, relaid};
+    std::copy(last, last + 5, ctx->sweep_last);
     return 0;
   }
   auto kern = labT ? (half ? k_sweep_spixl<32, true> : k_sweep_spixl<64, true>)
@@ -1196,6 +1204,8 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
   hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((nb + 7) / 8)), (unsigned)(z1 - z0)), dim3(256), 0, s,
                      (const float4*)lab, spixl, rep, levels, vs, sn, a, wps, labT, tslot, tstride);
   MVS_LAUNCH_CHECK("k_sweep_spixl");
+  const int last[5] = {labT ? 3 : hz ? 1 : 0, half ? 32 : 64, half ? 1 : wps, tmode, relaid};
+  std::copy(last, last + 5, ctx->sweep_last);
   return 0;
 }
 

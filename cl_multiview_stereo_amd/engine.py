@@ -192,6 +192,16 @@ class Engine:
                    "mvs_sweep_spixl_d")
         return spixl
 
+    def sweep_last_variant(self) -> dict:
+        """The last sweep_spixl launch: FORM (0 general gathers, 1 HZ gathers, 2 HZ
+        ring, 3 re-laid copies), LPS (lanes per superpixel, 32 | 64), WPS (waves per
+        superpixel), TMODE (MVS_SWEEP_TRANSPOSE in effect), RELAID ((view, kind)
+        copies built; 0: none needed, or the scratch fell back)."""
+        v = (C.c_int32 * 5)()
+        if self.L.mvs_sweep_last_variant_n(self.ctx, v, 5) != 5:
+            raise _lib.MvsError("mvs_sweep_last_variant_n: unexpected slot count")
+        return dict(zip(("FORM", "LPS", "WPS", "TMODE", "RELAID"), list(v)))
+
     def sweep_pixel_sad(self, lab, cam: CameraArray, z0: int = 0, z1: int | None = None, out=None):
         V, H, W, _ = lab.shape
         z1 = V if z1 is None else z1

@@ -190,6 +190,16 @@ int mvs_ncc_wta_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int
 int mvs_set_ncc_variant(mvs_ctx* ctx, int waves, int levels_per_wave, int band_w, int general_rows);
 int mvs_ncc_last_variant(mvs_ctx* ctx, int32_t* out7);
 int mvs_ncc_last_variant_n(mvs_ctx* ctx, int32_t* out, int cap);
+/* Test hook (0.8): the kernel form of the last mvs_sweep_spixl_d launch as
+ * {FORM, LPS, WPS, TMODE, RELAID}: FORM 0 the general row-major gathers, 1 the
+ * same-camera-row integer-shift (HZ) gathers, 2 the HZ form on LDS-staged rows,
+ * 3 the gathers from re-laid (transposed / sheared) neighbour copies; LPS the
+ * lanes per superpixel (32: two superpixels per wave, 64); WPS the waves per
+ * superpixel; TMODE the transposition mode in effect (MVS_SWEEP_TRANSPOSE);
+ * RELAID the number of (view, kind) copies built, 0 when none was needed or
+ * the scratch could not be had.  Writes the first min(cap, 5) slots and
+ * returns 5, the slots it has. */
+int mvs_sweep_last_variant_n(mvs_ctx* ctx, int32_t* out, int cap);
 /* Kernel timing (a measurement aid, no reference counterpart): with timing on,
  * every fused NCC sweep launch (mvs_ncc_wta_d / mvs_ncc_wta_range_d) records
  * start / stop events of its own dispatch (hipExtLaunchKernel), so the time is
