@@ -153,7 +153,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.8 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.9 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -403,6 +403,28 @@ int mvs_ncc_wta_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32
 int mvs_wta_d(mvs_ctx* c, int W, int H, int D, const float* vol, const float* levels, float* disp, float* conf) {
   if (!c || !vol || !levels || !disp || D <= 0 || bad_dims(W, H)) return mvs::arg_fail("mvs_wta_d: bad arguments");
   return mvs::launch_wta(c->stream, W, H, D, vol, levels, disp, conf);
+}
+
+int mvs_wta_sub_d(mvs_ctx* c, int W, int H, int D, const float* vol, const float* levels, float* disp_sub) {
+  if (!c || !vol || !levels || !disp_sub || D <= 0 || bad_dims(W, H))
+    return mvs::arg_fail("mvs_wta_sub_d: bad arguments");
+  return mvs::launch_wta_sub(c->stream, W, H, D, vol, levels, disp_sub);
+}
+
+int mvs_ncc_sub_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,
+                        int z0, int z1, const float* disp, float* disp_sub) {
+  if (!c || !l8 || !box || !disp || !disp_sub || bad_dims(W, H))
+    return mvs::arg_fail("mvs_ncc_sub_range_d: bad arguments");
+  if (W < 2) return mvs::arg_fail("mvs_ncc_sub_range_d: NCC sweep needs W >= 2");
+  if (K != 5 && K != 7) return mvs::arg_fail("mvs_ncc_sub_range_d: NCC window must be 5 or 7");
+  RC(upload_meta(c, a));
+  if (z0 < 0 || z1 > a->view_count || z0 > z1) return mvs::arg_fail("mvs_ncc_sub_range_d: bad view range");
+  // the winner's index is recovered from its level by value
+  for (int i = 1; i < a->num_levels; i++)
+    if (!(a->levels[i - 1] < a->levels[i]))
+      return mvs::arg_fail("mvs_ncc_sub_range_d: levels must be strictly increasing");
+  return mvs::launch_ncc_sub(c->stream, a->view_count, W, H, box, c->d_levels, a->num_levels, c->d_vs, c->d_sn,
+                             a->array_width, a->bl_ratio, K, z0, z1, disp, disp_sub);
 }
 
 int mvs_flatness_d(mvs_ctx* c, int V, int mw, int mh, const float* spixl, float gamma, float* flat) {

@@ -312,6 +312,34 @@ class Engine:
                                     _ptr(conf) if want_conf else None), "mvs_wta_d")
         return disp, conf
 
+    def wta_sub(self, vol, levels: torch.Tensor, out=None):
+        """Sub-level disparity over a materialised volume [D, H, W]: the parabola fit through
+        the winner's cost and its two neighbours' in level order (include/mvs.h)."""
+        D, H, W = vol.shape
+        out = self.empty((H, W), torch.float32) if out is None else out
+        if tuple(out.shape) != (H, W) or tuple(levels.shape) != (D,):
+            raise ValueError("wta_sub: out must be [H, W], levels [D]")
+        self._stream()
+        _lib.check(self.L.mvs_wta_sub_d(self.ctx, W, H, D, _ptr(vol), _ptr(levels), _ptr(out)), "mvs_wta_sub_d")
+        return out
+
+    def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):
+        """The same for reference views [z0, z1) without a volume: disp [z1 - z0, H, W] is what
+        ncc_wta_range wrote; the three costs are recomputed from the window planes (bit-identical
+        to ncc_volume + wta_sub per view).  out may be disp (in place)."""
+        V, H, W = l8.shape
+        n = z1 - z0
+        if disp is None:
+            raise ValueError("ncc_sub_range needs the integer-level disp of ncc_wta_range")
+        out = self.empty((n, H, W), torch.float32) if out is None else out
+        for t in (disp, out):
+            if tuple(t.shape) != (n, H, W) or not t.is_contiguous():
+                raise ValueError("disp / out must be contiguous [z1 - z0, H, W]")
+        self._stream()
+        _lib.check(self.L.mvs_ncc_sub_range_d(self.ctx, W, H, _ptr(l8), _ptr(box), cam.desc(), K, int(z0), int(z1),
+                                              _ptr(disp), _ptr(out)), "mvs_ncc_sub_range_d")
+        return out
+
     # ---- refinement ------------------------------------------------------
     def refine(self, spixl, labels, rep, cam: CameraArray, S: int, gamma=2.0, alpha=6.0, fuse=1.0, kernel_step=13,
                kernel_size=1080, no_prop=5, fusion_compat=True, want_disp=True):

@@ -62,12 +62,17 @@ class PixelSweep:
     [D][H][W] per reference view, then WTA + confidence (the HBM-streaming
     pass); fused=True folds the WTA into the sweep kernel (mvs_ncc_wta_d: no
     volume in HBM, same disp/conf bits).  cost="sad": the reference sweep at
-    S=1 grid semantics (parity)."""
+    S=1 grid semantics (parity).  subpixel=True (NCC only): run() also leaves
+    the sub-level disparity (the parabola fit of include/mvs.h) of the views
+    it swept in self.disp_sub; disp and conf are unchanged."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
-                 fused: bool = False):
+                 fused: bool = False, subpixel: bool = False):
+        if subpixel and cost != "ncc":
+            raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
         self.e, self.cam, self.W, self.H = engine, cam, W, H
-        self.cost, self.K, self.fused = cost, window, fused
+        self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
+        self.disp_sub = None
         self.vol = None
         if cost == "ncc" and not fused:
             self.vol = engine.empty((cam.D, H, W), torch.float32)
@@ -90,10 +95,16 @@ class PixelSweep:
             box = self.e.box_stats_views(l8, self.K, views, self.e.empty((2, V, H + (H & 1), W, 2), torch.int32))
         if self.fused:  # every reference view of the call, runs of views per launch
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
+            if self.subpixel:  # the post-pass over the whole range, one call
+                self.disp_sub = self.e.ncc_sub_range(l8, box, self.cam, z0, z1, self.K, disp=disp)
             return disp, conf
+        if self.subpixel:
+            self.disp_sub = self.e.empty((n, self.H, self.W), torch.float32)
         for i, z in enumerate(range(z0, z1)):
             self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
             self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
+            if self.subpixel:
+                self.e.wta_sub(self.vol, self.levels, out=self.disp_sub[i])
         return disp, conf
 
 
@@ -125,6 +136,7 @@ class StepOutput:
     rep: torch.Tensor
     disp: torch.Tensor | None = None
     conf: torch.Tensor | None = None
+    disp_sub: torch.Tensor | None = None  # sub-level disparity (Pipeline(subpixel=True)), else None
     disp_refined: torch.Tensor | None = None
     disp_filtered: torch.Tensor | None = None
 
@@ -147,7 +159,8 @@ class Pipeline:
 
     def __init__(self, engine: Engine, settings: params.Settings, W: int, H: int,
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
-                 refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False):
+                 refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
+                 subpixel: bool = False):
         self.e, self.st, self.W, self.H = engine, settings, W, H
         vs = view_subset if view_subset is not None else params.neighbour_lists(
             settings.array_width, settings.array_height, settings.neib_hor, settings.neib_ver)
@@ -156,7 +169,10 @@ class Pipeline:
         self.cam = CameraArray(settings.array_width, settings.bl_ratio, levels, mat, num)
         self.slic = SLIC(engine, settings)
         self.photo = PhotoConsistency(engine, self.cam, settings.spixl_size)
-        self.pixel = PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused) if pixel_cost else None
+        if subpixel and pixel_cost != "ncc":
+            raise ValueError("subpixel=True needs pixel_cost=\"ncc\"")
+        self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel)
+                      if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None
         self.side = None
@@ -191,6 +207,8 @@ class Pipeline:
             for t in (spixl, labels, rep):  # allocated on the side stream, used on main from here
                 t.record_stream(main)
             out = StepOutput(lab, spixl, labels, rep, disp, conf)
+        if self.pixel is not None and self.pixel.subpixel:
+            out.disp_sub = self.pixel.disp_sub
         if self.refiner is not None:
             r = self.refiner.do_refinement(spixl, labels, rep, self.st)
             out.disp_refined = r["disp"]

@@ -176,6 +176,29 @@ int mvs_ncc_wta_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int32_t* 
  * reference view, photo_consistency.cpp:133). */
 int mvs_ncc_wta_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a,
                         int K, int z0, int z1, float* disp, float* conf);
+/* Sub-level disparity (0.9): a three-point parabola fit through the costs of
+ * the winning level and its two neighbours in level order.  All arithmetic is
+ * float32, each operation rounded, no fused multiply-add.  For a pixel with
+ * costs vol[0..D-1] and levels[0..D-1]:
+ *   b    = first index of the minimum in level order, strict < (mvs_wta_d's rule)
+ *   cm, c0, cp = vol[b-1], vol[b], vol[b+1]
+ *   ok   = 0 < b < D-1 and cm < 2 and cp < 2   (a cost of 2: no valid window)
+ *   den  = (cm - c0) + (cp - c0)               (> 0 whenever ok)
+ *   off  = (0.5 * (cm - cp)) / den             (|off| <= 0.5; +0.5 iff cp == c0)
+ *   step = off < 0 ? levels[b] - levels[b-1] : levels[b+1] - levels[b]
+ *   disp_sub = ok ? levels[b] + off * step : levels[b]
+ * mvs_wta_sub_d applies it to a materialised volume: disp_sub [H][W]; levels
+ * (device pointer, [D]) need not be ordered. */
+int mvs_wta_sub_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, const float* levels, float* disp_sub);
+/* The same for reference views [z0, z1) without a volume: disp [z1-z0][H][W] is
+ * the integer-level winner mvs_ncc_wta_range_d wrote; disp_sub may be the same
+ * buffer (in place).  The three costs are recomputed from the box planes:
+ * bit-identical to mvs_ncc_volume_d + mvs_wta_sub_d per view.  The winner's
+ * index is recovered from its level by value, so a->levels must be strictly
+ * increasing (MVS_E_ARG otherwise, as for K other than 5 or 7 or a bad view
+ * range); a disparity that matches no level is copied.  l8 is validated only. */
+int mvs_ncc_sub_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a,
+                        int K, int z0, int z1, const float* disp, float* disp_sub);
 /* Tuning / test hook: the NCC sweep variant this context tries first (0 =
  * automatic): waves per workgroup 4|8, levels per wave 1|2|4,
  * minimum LDS band width 64|80|96|128|192|256 columns, general_rows 1 = the kernel
