@@ -40,10 +40,9 @@
 //     plane are one 16-byte LDS read), then v_max_f32 per cell;
 //   * the chunk's costs are written once, 64-column coalesced rows.
 #include <algorithm>
-#include <array>
+#include <string>
 #include <vector>
 #include <type_traits>
-#include <cstdlib>
 
 #include "ncc_common.h"
 
@@ -555,206 +554,53 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
   }
 }
 
-// Host side: the chunk/level shift plan (every roundf of the definition is
-// evaluated here, once per distinct configuration) and the launch.
-struct NccPlan {
-  std::vector<int32_t> table;  // NccRec [nchunks][nn][NW waves] as int32
-  int band_w = 0, pk_pairs = 0, st_pairs = 0;
-  bool even = true;  // every level's band rows start on a pair boundary (kParEven)
-  bool odd = true;   // every pk start odd, every stats start even (kParOdd)
-  int par() const { return even ? kParEven : odd ? kParOdd : kParMixed; }
-};
-
-inline int floor_half(int v) { return v >> 1; }  // arithmetic: floor(v / 2)
-
-template <int K, int TH, int DPW, int NW>
-NccPlan make_plan(const float* levels, int D, int nn, const float* fdx, const float* fdy, float bl) {
-  constexpr int R = K / 2, NR = TH + 2 * R, DC = NW * DPW;
-  static_assert(DPW <= 8, "NccRec holds 8 levels per wave");
-  constexpr int RW = sizeof(NccRec) / 4;
-  const int nch = (D + DC - 1) / DC;
-  NccPlan p;
-  p.table.assign((size_t)nch * nn * NW * RW, 0);
-  int spx = 0;
-  auto tx_of = [&](int dl, int n) { return (int)roundf(levels[dl] * fdx[n]); };
-  auto ty_of = [&](int dl, int n) { return (int)roundf((bl * levels[dl]) * fdy[n]); };
-  // y0 is even (TH even), so every row parity below is independent of y0
-  for (int c = 0; c < nch; c++)
-    for (int n = 0; n < nn; n++) {
-      int txmin = 1 << 30, txmax = -(1 << 30), tymin = 1 << 30, tymax = -(1 << 30);
-      for (int dl = c * DC; dl < std::min(D, c * DC + DC); dl++) {
-        txmin = std::min(txmin, tx_of(dl, n)); txmax = std::max(txmax, tx_of(dl, n));
-        tymin = std::min(tymin, ty_of(dl, n)); tymax = std::max(tymax, ty_of(dl, n));
-      }
-      const int pb = -R - tymax, sb = -tymax;            // band first image row - y0
-      const int pr = pb - 2 * floor_half(pb), sr = sb - 2 * floor_half(sb);  // its parity in the pair band
-      const int bhp = (pr + NR + tymax - tymin + 1) >> 1;  // pairs covering every level's rows
-      const int shp = (sr + TH + tymax - tymin + 1) >> 1;
-      for (int w = 0; w < NW; w++) {
-        int32_t* e = p.table.data() + (((size_t)c * nn + n) * NW + w) * RW;
-        e[0] = txmax;
-        e[1] = tymax;
-        e[2] = bhp;
-        e[3] = shp | ((txmax - txmin) << 16);  // stage(): pieces of 64 columns covering 64 + span
-        for (int j = 0; j < DPW; j++) {
-          const int dl = c * DC + w + NW * j;
-          if (dl >= D) {  // dummy level past the end: the band origin's even rows
-            e[4 + 2 * j] = 0;
-            e[5 + 2 * j] = pr | (sr << 16);  // same parity as the real levels'
-            continue;
-          }
-          const int ty = ty_of(dl, n);
-          e[4 + 2 * j] = txmax - tx_of(dl, n);
-          e[5 + 2 * j] = (pr + tymax - ty) | ((sr + tymax - ty) << 16);
-          if (((pr + tymax - ty) | (sr + tymax - ty)) & 1) p.even = false;
-          if (!((pr + tymax - ty) & 1) || ((sr + tymax - ty) & 1)) p.odd = false;
-        }
-      }
-      spx = std::max(spx, txmax - txmin);
-      p.pk_pairs = std::max(p.pk_pairs, bhp);
-      p.st_pairs = std::max(p.st_pairs, shp);
-    }
-  p.band_w = 64 + spx;  // columns per pair row (stage() never writes past them)
-  return p;
-}
-
-template <int K, int TH, int DPW, int NW, int BW, int PAR, int NB = 2>
-int launch_ncc_bw(mvs_ctx* ctx, const uint2* stats, const uint2* pk, const NccRec* plan, NccArgs& a, float* vol,
-                  const WtaOut& wo, size_t lds) {
-  hipStream_t s = ctx->stream;
-  const int variant[8] = {K, TH, DPW, NW, BW, PAR, vol ? 0 : 1, NB};
-  std::copy(variant, variant + 8, ctx->ncc_last);
-  constexpr int DC = NW * DPW;
-  a.tiles_x = (a.W + 63) / 64;
-  a.ntiles = a.tiles_x * ((a.H + TH - 1) / TH);
-  a.tiles_per_xcd = (a.nref * a.ntiles + 7) / 8;
-  a.nch = (a.D + DC - 1) / DC;
-  dim3 g(8 * a.tiles_per_xcd);
+// Host side: the launch planner (ncc_plan.cpp) decides everything; here an
+// NccLaunch of the scalar family is mapped to its k_ncc_volume instantiation.
+template <int K, int DPW, int NW, int BW, int PAR, int NB>
+int launch_ncc_bw(const NccCall& c) {
+  constexpr int TH = kTileH;
+  float* vol = c.vol;
+  const size_t lds = c.L.lds;
   auto kern = vol ? k_ncc_volume<K, TH, DPW, NW, BW, PAR, false, NB> : k_ncc_volume<K, TH, DPW, NW, BW, PAR, true, NB>;
-  if (!vol) lds = std::max(lds, (size_t)3 * 4 * NW * TH * 64) + 4 * TH * 64;  // WTA partials; + s_r [64][TH]
-  MVS_HIP(raise_lds(ctx, (const void*)kern, lds), "hipFuncSetAttribute(ncc lds)");
-  const auto ev = vol ? std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr} : kernel_events(ctx);  // (the fused sweep only)
-  hipExtLaunchKernelGGL(kern, g, dim3(NW * 64), lds, s, ev.first, ev.second, 0, stats, pk, plan, a, vol, wo);
+  MVS_HIP(raise_lds(c.ctx, (const void*)kern, lds), "hipFuncSetAttribute(ncc lds)");
+  const auto ev = vol ? std::pair<hipEvent_t, hipEvent_t>{nullptr, nullptr} : kernel_events(c.ctx);  // (the fused sweep only)
+  hipExtLaunchKernelGGL(kern, dim3(8 * c.L.args.tiles_per_xcd), dim3(NW * 64), lds, c.ctx->stream, ev.first, ev.second,
+                        0, c.stats, c.pk, (const NccRec*)c.plan, c.L.args, vol, c.wo);
   MVS_LAUNCH_CHECK(vol ? "k_ncc_volume" : "k_ncc_volume (fused WTA)");
   return 0;
 }
-
-// One reference view's variant: its shift plan for (K, TH = 8, DPW, NW) and
-// the band pair-row stride, if its double-buffered bands fit `cap` bytes of LDS.
-struct NccChoice {
-  int dpw = 0, nw = 0, bwt = 0, nb = 2;  // nb: band buffers (k_ncc_volume's NB)
-  size_t cap = 0;
-  NccPlan plan;
-};
-template <int K, int DPW, int NW>
-bool try_plan(const mvs_ctx* ctx, const float* levels, int D, int nn, const float* fdx, const float* fdy, float bl,
-              size_t cap, NccChoice& o, int nb = 2) {
-  NccPlan p = make_plan<K, 8, DPW, NW>(levels, D, nn, fdx, fdy, bl);
-  // the band's pair-row stride is the template BW: the smallest of 64 / 80 /
-  // 96 / 128 / 192 / 256 holding band_w, or a wider one forced through
-  // mvs_set_ncc_variant.  A vertical-only list needs 64, a diagonal or
-  // horizontal neighbour 64 + the chunk's shift range (C4: 71 / 79 / 95)
-  const int bw = std::max(p.band_w, ctx->ncc_bw);
-  const int bwt = bw <= 64 ? 64 : bw <= 80 ? 80 : bw <= 96 ? 96 : bw <= 128 ? 128 : bw <= 192 ? 192 : 256;
-  const size_t lds = nb * 16 * (size_t)(p.pk_pairs + p.st_pairs) * bwt;
-  if (lds > cap || bw > 256) return false;
-  o.nb = nb;
-  o.dpw = DPW;
-  o.nw = NW;
-  o.bwt = bwt;
-  o.cap = cap;
-  o.plan = std::move(p);
-  return true;
-}
-// waves per workgroup and levels per wave: MVS_NCC_NW (4|8), MVS_NCC_DPW
-// (1|2|4), or the context's override (mvs_set_ncc_variant), tried first.
-// Then the widest variant whose double-buffered bands leave room for two
-// workgroups per CU (vertical shifts grow the bands: fewer levels per step
-// then beat a single resident workgroup), then any that fits the LDS.
-template <int K>
-bool choose_variant(const mvs_ctx* ctx, const float* levels, int D, int nn, const float* fdx, const float* fdy,
-                    float bl, NccChoice& o) {
-  static const int dpw_env = [] {
-    const char* e = getenv("MVS_NCC_DPW");
-    return e ? atoi(e) : 4;
-  }();
-  static const int nw_env = [] {
-    const char* e = getenv("MVS_NCC_NW");
-    return e ? atoi(e) : 8;
-  }();
-  const int dpw_pref = ctx->ncc_dpw ? ctx->ncc_dpw : dpw_env;
-  const int nw_pref = ctx->ncc_nw ? ctx->ncc_nw : nw_env;
-  bool ok = false;
-#define MVS_NCC_TRY(DD, WW) \
-  if (!ok) ok = try_plan<K, DD, WW>(ctx, levels, D, nn, fdx, fdy, bl, cap, o);
-  if (ctx->ncc_nw || ctx->ncc_dpw) {  // a forced variant is tried first, at the full LDS
-    const size_t cap = (size_t)160 * 1024;
-    if (nw_pref >= 8 && dpw_pref >= 4) {
-      MVS_NCC_TRY(4, 8)
-    } else if (nw_pref >= 8 && dpw_pref >= 2) {
-      MVS_NCC_TRY(2, 8)
-    } else if (dpw_pref >= 4) {
-      MVS_NCC_TRY(4, 4)
-    } else if (dpw_pref >= 2) {
-      MVS_NCC_TRY(2, 4)
-    } else {
-      MVS_NCC_TRY(1, 4)
-    }
-  }
-  // A K = 5 list whose double-buffered 32-level bands miss two workgroups per
-  // CU (C4's 5-NN lists: vertical and diagonal bands) tries them single-
-  // buffered before halving the chunk (k_ncc_volume's NB), and a list too
-  // tall even for that (C4's corner views: a neighbour two rows away) takes
-  // 8 waves x 2 levels single-buffered before 4 waves: C4 step 48.1 -> 46.6 ms,
-  // fused sweep 0.71 -> 0.66 ms per view (interleaved A/B,
-  // profiles/r04/abenv_c4_nb1_corner.txt).  MVS_NCC_NB=2 (read per call)
-  // keeps the double-buffered forms.
-  const char* nbe = getenv("MVS_NCC_NB");
-  const bool nb1 = K == 5 && !(nbe && atoi(nbe) == 2);
-  for (size_t cap : {(size_t)80 * 1024, (size_t)160 * 1024}) {
-    if (nw_pref >= 8 && dpw_pref >= 4) MVS_NCC_TRY(4, 8)
-    if (nb1 && cap <= 80 * 1024 && nw_pref >= 8 && dpw_pref >= 4 && !ok)
-      ok = try_plan<K, 4, 8>(ctx, levels, D, nn, fdx, fdy, bl, cap, o, 1);
-    if (nw_pref >= 8 && dpw_pref >= 2) MVS_NCC_TRY(2, 8)
-    if (nb1 && cap <= 80 * 1024 && nw_pref >= 8 && dpw_pref >= 2 && !ok)  // (C4's corner views)
-      ok = try_plan<K, 2, 8>(ctx, levels, D, nn, fdx, fdy, bl, cap, o, 1);
-    if (dpw_pref >= 4) MVS_NCC_TRY(4, 4)
-    if (dpw_pref >= 2) MVS_NCC_TRY(2, 4)
-    MVS_NCC_TRY(1, 4)
-  }
-#undef MVS_NCC_TRY
-  return ok;
-}
-
 template <int K, int DPW, int NW, int PAR, int NB = 2>
-int launch_bw(mvs_ctx* ctx, int bwt, const uint2* stats, const uint2* pk, const NccRec* plan, NccArgs& a, float* vol,
-              const WtaOut& wo, size_t lds) {
-  if (bwt == 64) return launch_ncc_bw<K, 8, DPW, NW, 64, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
-  if (bwt == 80) return launch_ncc_bw<K, 8, DPW, NW, 80, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
-  if (bwt == 96) return launch_ncc_bw<K, 8, DPW, NW, 96, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
-  if (bwt == 128) return launch_ncc_bw<K, 8, DPW, NW, 128, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
-  if (bwt == 192) return launch_ncc_bw<K, 8, DPW, NW, 192, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
-  return launch_ncc_bw<K, 8, DPW, NW, 256, PAR, NB>(ctx, stats, pk, plan, a, vol, wo, lds);
+int launch_bw(const NccCall& c) {
+  switch (c.L.BW) {
+    case 64: return launch_ncc_bw<K, DPW, NW, 64, PAR, NB>(c);
+    case 80: return launch_ncc_bw<K, DPW, NW, 80, PAR, NB>(c);
+    case 96: return launch_ncc_bw<K, DPW, NW, 96, PAR, NB>(c);
+    case 128: return launch_ncc_bw<K, DPW, NW, 128, PAR, NB>(c);
+    case 192: return launch_ncc_bw<K, DPW, NW, 192, PAR, NB>(c);
+    case 256: return launch_ncc_bw<K, DPW, NW, 256, PAR, NB>(c);
+  }
+  return no_kernel();
 }
 // the parity-specific kernels only where they occur: kParEven for K = 5
-// (horizontal bands, R = 2), kParOdd for K = 7 (R = 3)
+// (horizontal bands, R = 2), kParOdd for K = 7 (R = 3); single-buffered bands
+// (C4's tall 5-NN bands, any parity) for K = 5 at 8 waves x 2 or 4 levels
 template <int K, int DPW, int NW>
-int launch_bw_par(mvs_ctx* ctx, int bwt, int par, const uint2* stats, const uint2* pk, const NccRec* plan,
-                  NccArgs& a, float* vol, const WtaOut& wo, size_t lds, int nb) {
+int launch_bw_par(const NccCall& c) {
   constexpr int KPAR = K == 5 ? kParEven : kParOdd;
-  if constexpr (K == 5 && DPW >= 2 && NW == 8)  // single-buffered bands: C4's tall 5-NN bands (any parity)
-    if (nb == 1) return launch_bw<K, DPW, NW, kParMixed, 1>(ctx, bwt, stats, pk, plan, a, vol, wo, lds);
-  if (par == KPAR && !ctx->ncc_general) return launch_bw<K, DPW, NW, KPAR>(ctx, bwt, stats, pk, plan, a, vol, wo, lds);
-  return launch_bw<K, DPW, NW, kParMixed>(ctx, bwt, stats, pk, plan, a, vol, wo, lds);
+  if constexpr (K == 5 && DPW >= 2 && NW == 8)
+    if (c.L.NB == 1 && c.L.PAR == kParMixed) return launch_bw<K, DPW, NW, kParMixed, 1>(c);
+  if (c.L.NB != 2) return no_kernel();
+  if (c.L.PAR == KPAR) return launch_bw<K, DPW, NW, KPAR>(c);
+  return c.L.PAR == kParMixed ? launch_bw<K, DPW, NW, kParMixed>(c) : no_kernel();
 }
 template <int K>
-int launch_variant(mvs_ctx* ctx, const NccChoice& c, int bwt, int par, const uint2* stats, const uint2* pk,
-                   const NccRec* plan, NccArgs& a, float* vol, const WtaOut& wo, size_t lds) {
-  if (c.dpw == 4 && c.nw == 8) return launch_bw_par<K, 4, 8>(ctx, bwt, par, stats, pk, plan, a, vol, wo, lds, c.nb);
-  if (c.dpw == 2 && c.nw == 8) return launch_bw_par<K, 2, 8>(ctx, bwt, par, stats, pk, plan, a, vol, wo, lds, c.nb);
-  if (c.dpw == 4) return launch_bw_par<K, 4, 4>(ctx, bwt, par, stats, pk, plan, a, vol, wo, lds, c.nb);
-  if (c.dpw == 2) return launch_bw_par<K, 2, 4>(ctx, bwt, par, stats, pk, plan, a, vol, wo, lds, c.nb);
-  return launch_bw_par<K, 1, 4>(ctx, bwt, par, stats, pk, plan, a, vol, wo, lds, c.nb);
+int launch_variant(const NccCall& c) {
+  const int dpw = c.L.DPW, nw = c.L.NW;
+  if (dpw == 4 && nw == 8) return launch_bw_par<K, 4, 8>(c);
+  if (dpw == 2 && nw == 8) return launch_bw_par<K, 2, 8>(c);
+  if (dpw == 4 && nw == 4) return launch_bw_par<K, 4, 4>(c);
+  if (dpw == 2 && nw == 4) return launch_bw_par<K, 2, 4>(c);
+  return dpw == 1 && nw == 4 ? launch_bw_par<K, 1, 4>(c) : no_kernel();
 }
 
 }  // namespace
@@ -774,202 +620,31 @@ int launch_box_stats(hipStream_t s, const uint8_t* l8, int V, int W, int H, int 
   return 0;
 }
 
-// Reference views [z0, z1): each view's variant is chosen on its own shifts;
-// runs of consecutive views with the same (DPW, NW) whose merged bands still
-// fit every member's LDS cap share one launch (up to kMaxRef views, fused
-// sweep only: a cost volume holds one view), with the widest band stride and
-// a parity-specific kernel only when every member has that parity -- the same arithmetic,
-// one kernel boundary (~11 us between two of these launches) per run.
+// Reference views [z0, z1): plan_ncc_launches (ncc_plan.cpp) chooses each
+// view's kernel form and merges runs of views into launches; each launch's
+// table is uploaded (cached per context) and its kernel dispatched.
 int launch_ncc_refs(mvs_ctx* ctx, int V, int W, int H, const int32_t* box, const float* levels_host, int D,
                     const int* vs_host, const int* sn_host, int aw, float bl, int K, int z0, int z1, float* vol,
                     const float* levels_dev, float* disp, float* conf) {
   if (!vol && (!levels_dev || !disp)) return arg_fail("fused NCC sweep needs levels and disp");
-  if (vol && z1 - z0 != 1) return arg_fail("the NCC cost volume holds one reference view");
-  if (W < 2) return arg_fail("NCC sweep needs W >= 2");
-  if (K != 5 && K != 7) return arg_fail("NCC window must be 5 or 7");
-  if (!vol && D > 65535) return arg_fail("fused NCC sweep: at most 65535 levels");  // K = 7 packs levels in 16 bits
-  const int n = z1 - z0;
-  if (n <= 0) return 0;
-  std::vector<NccChoice> ch(n);
-  std::vector<std::array<int, kMaxNbr>> views(n);
-  // the matrix-core form (k_ncc_mfma) for fused K = 5 views: horizontal lists
-  // (every vertical shift 0) in 32-level double-buffered chunks; lists with
-  // vertical / diagonal neighbours (VERT) in the first of 32-level double- /
-  // single-buffered, 16-level double- / single-buffered chunks whose bands
-  // leave two workgroups per CU (80 KB).  MVS_NCC_MFMA=0 (read per call) or a
-  // forced variant (mvs_set_ncc_variant) keeps the scalar kernels.  VERT
-  // lists take the matrix-core form by default (MVS_NCC_MFMA_V unset or 1:
-  // the launcher's choice under two workgroups per CU; 22 | 21 | 12 | 11:
-  // that form; 0: the scalar kernels).  Since its finish went scalar f32 it
-  // runs C4's 5-NN lists ~1 % faster than the scalar kernels
-  // K = 7 (C5): horizontal lists in 16-level chunks (its 2 x 8-pixel blocks'
-  // operands take 32 VGPRs); MVS_NCC_MFMA7=0 keeps the scalar kernels (A/B)
-  const char* mfe = getenv("MVS_NCC_MFMA");
-  const char* mfv = getenv("MVS_NCC_MFMA_V");
-  const char* mf7 = getenv("MVS_NCC_MFMA7");
-  // (its band DMA addresses one view's plane by 32-bit byte offsets)
-  const bool mf_on = !vol && (K == 5 || (K == 7 && !(mf7 && atoi(mf7) == 0))) && !(mfe && atoi(mfe) == 0) &&
-                     !ctx->ncc_nw && !ctx->ncc_dpw && !ctx->ncc_general && !ctx->ncc_bw &&
-                     (long)W * (H + (H & 1)) * 8 < 0x7fffffffL;
-  const int mfv_form = mfv ? atoi(mfv) : 1;  // 0: off, 1: automatic (default), else the form
-  std::vector<char> mf(n, 0);
-  std::vector<NccPlanM> mplan(n);
-  std::vector<int> mnb(n, 2);
-  for (int r = 0; r < n; r++) {
-    const int z = z0 + r, nn = sn_host[z];
-    if (nn > kMaxNbr) return arg_fail("NCC sweep supports at most 16 neighbours per reference view");
-    float fdx[kMaxNbr], fdy[kMaxNbr];
-    const int rx = z % aw, ry = z / aw;
-    bool horiz = true;
-    for (int k = 0; k < nn; k++) {
-      const int v = vs_host[V * z + k];
-      if (v < 0 || v >= V) return arg_fail("view_subset entry out of range");
-      views[r][k] = v;
-      fdx[k] = (float)(v % aw - rx);
-      fdy[k] = (float)(v / aw - ry);
-      if (fdy[k] != 0.0f) horiz = false;
-    }
-    if (mf_on && horiz && nn > 0) {
-      const int ndb = K == 5 ? 2 : 1;
-      mplan[r] = make_plan_mfma(levels_host, D, nn, fdx, fdy, bl, ndb, K);
-      // the run keeps every step's level offsets in LDS (tmax = chunks x
-      // neighbours): past the 160 KB of a CU (large D with many neighbours)
-      // the scalar kernels take the view
-      const int tm = ((D + 16 * ndb - 1) / (16 * ndb)) * nn;
-      if (mplan[r].band_w <= 192 && mfma_lds_bytes(mplan[r], mplan[r].band_w, 2, tm, D) <= (size_t)160 * 1024) {
-        mf[r] = 1;
-        continue;
-      }
-    }
-    if (mf_on && K == 5 && !horiz && nn > 0 && mfv_form != 0) {
-      static const int forms[4][2] = {{2, 2}, {2, 1}, {1, 2}, {1, 1}};
-      for (const auto& f : forms) {
-        const bool forced = mfv_form > 1;
-        if (forced && mfv_form != 10 * f[0] + f[1]) continue;
-        NccPlanM pm = make_plan_mfma(levels_host, D, nn, fdx, fdy, bl, f[0]);
-        const int tm = ((D + 16 * f[0] - 1) / (16 * f[0])) * nn;
-        const size_t cap = forced ? (size_t)160 * 1024 : (size_t)80 * 1024;
-        if (pm.band_w <= 128 && mfma_lds_bytes(pm, pm.band_w, f[1], tm, D) <= cap) {
-          mplan[r] = std::move(pm);
-          mnb[r] = f[1];
-          mf[r] = 1;
-          break;
-        }
-      }
-      if (mf[r]) continue;
-    }
-    const bool ok = K == 5 ? choose_variant<5>(ctx, levels_host, D, nn, fdx, fdy, bl, ch[r])
-                           : choose_variant<7>(ctx, levels_host, D, nn, fdx, fdy, bl, ch[r]);
-    if (!ok) return arg_fail("NCC sweep: neighbour shifts too large for the LDS band");
-  }
+  const NccTuning tuning = ncc_tuning(ctx->ncc_nw, ctx->ncc_dpw, ctx->ncc_bw, ctx->ncc_general);
+  std::vector<NccLaunch> launches;
+  std::string err;
+  if (!plan_ncc_launches(tuning, V, W, H, K, D, levels_host, vs_host, sn_host, aw, bl, z0, z1, vol != nullptr,
+                         launches, err))
+    return arg_fail(err.c_str());
   const uint2* stats = (const uint2*)box;
   const uint2* pk = stats + (long)V * W * (H + (H & 1));
-  constexpr int RW = sizeof(NccRec) / 4;
   const long P = (long)W * H;
-  // MVS_NCC_RUN (read per call): views per launch at most (A/B; default kMaxRef)
-  const char* re = getenv("MVS_NCC_RUN");
-  const int maxrun = re ? std::max(1, std::min(kMaxRef, atoi(re))) : kMaxRef;
-  for (int i = 0; i < n;) {
-    if (mf[i]) {  // a run of matrix-core views of one form: one launch, the widest band, the tallest bands
-      const bool vert = mplan[i].vert;
-      const int ndb = mplan[i].ndb, nb = mnb[i];
-      int j = i, bw = 0, tmax = 0;
-      NccArgs a{};
-      a.W = W;
-      a.H = H;
-      a.D = D;
-      std::vector<int32_t> table;
-      NccPlanM run;  // the run's band extents (LDS check)
-      run.ndb = ndb;
-      run.vert = vert;
-      while (j < n && mf[j] && j - i < maxrun && mplan[j].vert == vert && mplan[j].ndb == ndb && mnb[j] == nb) {
-        const int z = z0 + j;
-        run.pk_pairs = std::max(run.pk_pairs, mplan[j].pk_pairs);
-        run.st_pairs = std::max(run.st_pairs, mplan[j].st_pairs);
-        const int bw2 = std::max(bw, mplan[j].band_w);
-        const int tm2 = std::max(tmax, ((D + 16 * ndb - 1) / (16 * ndb)) * sn_host[z]);
-        if (j > i && mfma_lds_bytes(run, bw2, nb, tm2, D) > (size_t)(vert ? 80 : 160) * 1024) break;
-        bw = bw2;
-        tmax = tm2;
-        a.z[j - i] = z;
-        a.nn[j - i] = sn_host[z];
-        a.plan[j - i] = (int)(table.size() / 32);  // 128-B NccMRec records
-        for (int k = 0; k < sn_host[z]; k++) a.view[j - i][k] = views[j][k];
-        // each record's neighbour plane as a byte offset (words 22, 23): the
-        // kernel rebases its band DMA on it with no per-step multiply
-        const size_t r0 = table.size();
-        table.insert(table.end(), mplan[j].table.begin(), mplan[j].table.end());
-        for (size_t rr = r0; rr < table.size(); rr += 32) {
-          const int nloc = (int)((rr - r0) / 32) % sn_host[z];
-          const unsigned long long off = (unsigned long long)views[j][nloc] * (unsigned long long)W *
-                                         (unsigned long long)((H + 1) >> 1) * 16ull;  // Pv uint2 = 16 B per (pair row, column)
-          table[rr + 22] = (int32_t)(off & 0xffffffffull);
-          table[rr + 23] = (int32_t)(off >> 32);
-          a.txmax_all = std::max(a.txmax_all, table[rr]);
-        }
-        j++;
-      }
-      a.nref = j - i;
-      a.pk_pairs = 0;
-      a.st_pairs = 0;
-      for (int r = i; r < j; r++) {
-        a.pk_pairs = std::max(a.pk_pairs, mplan[r].pk_pairs);
-        a.st_pairs = std::max(a.st_pairs, mplan[r].st_pairs);
-      }
-      int rc = 0;
-      const int32_t* dev = plan_upload(ctx, table, &rc);
-      if (rc) return rc;
-      const WtaOut wo{levels_dev, disp + P * i, conf ? conf + P * i : nullptr};
-      rc = launch_ncc_mfma(ctx, stats, pk, dev, a, wo, bw, tmax, vert, ndb, nb, K);
-      if (rc) return rc;
-      i = j;
-      continue;
-    }
-    int bwt = ch[i].bwt, pkp = ch[i].plan.pk_pairs, stp = ch[i].plan.st_pairs;
-    int par = ch[i].plan.par();
-    size_t cap = ch[i].cap;
-    int j = i + 1;
-    while (!vol && j < n && !mf[j] && j - i < maxrun && ch[j].dpw == ch[i].dpw && ch[j].nw == ch[i].nw &&
-           ch[j].nb == ch[i].nb) {
-      const int b2 = std::max(bwt, ch[j].bwt);
-      const int p2 = std::max(pkp, ch[j].plan.pk_pairs), s2 = std::max(stp, ch[j].plan.st_pairs);
-      const size_t c2 = std::min(cap, ch[j].cap);
-      if (ch[i].nb * 16 * (size_t)(p2 + s2) * b2 > c2) break;
-      bwt = b2;
-      pkp = p2;
-      stp = s2;
-      cap = c2;
-      if (ch[j].plan.par() != par) par = kParMixed;
-      j++;
-    }
-    NccArgs a{};
-    a.W = W;
-    a.H = H;
-    a.D = D;
-    // (band DMA by 32-bit buffer offsets; MVS_NCC_PLANE32=0, read per call: the 64-bit addresses, A/B)
-    const char* p32 = getenv("MVS_NCC_PLANE32");
-    a.plane32 = (long)W * (H + (H & 1)) * 8 < 0x7fffffffL && !(p32 && atoi(p32) == 0);
-    a.nref = j - i;
-    a.pk_pairs = pkp;
-    a.st_pairs = stp;
-    std::vector<int32_t> table;
-    for (int r = i; r < j; r++) {
-      const int z = z0 + r;
-      a.z[r - i] = z;
-      a.nn[r - i] = sn_host[z];
-      a.plan[r - i] = (int)(table.size() / RW);
-      for (int k = 0; k < sn_host[z]; k++) a.view[r - i][k] = views[r][k];
-      table.insert(table.end(), ch[r].plan.table.begin(), ch[r].plan.table.end());
-    }
+  for (const NccLaunch& L : launches) {
     int rc = 0;
-    const int32_t* dev = plan_upload(ctx, table, &rc);
+    const int32_t* dev = plan_upload(ctx, L.table, &rc);
     if (rc) return rc;
-    const WtaOut wo{levels_dev, disp ? disp + P * i : nullptr, conf ? conf + P * i : nullptr};
-    const size_t lds = ch[i].nb * 16 * (size_t)(pkp + stp) * bwt;
-    rc = K == 5 ? launch_variant<5>(ctx, ch[i], bwt, par, stats, pk, (const NccRec*)dev, a, vol, wo, lds)
-                : launch_variant<7>(ctx, ch[i], bwt, par, stats, pk, (const NccRec*)dev, a, vol, wo, lds);
+    std::copy(L.last, L.last + 8, ctx->ncc_last);
+    const WtaOut wo{levels_dev, disp ? disp + P * L.first : nullptr, conf ? conf + P * L.first : nullptr};
+    const NccCall c{ctx, L, stats, pk, dev, vol, wo};
+    rc = L.mfma ? launch_ncc_mfma(c) : L.K == 5 ? launch_variant<5>(c) : launch_variant<7>(c);
     if (rc) return rc;
-    i = j;
   }
   return 0;
 }

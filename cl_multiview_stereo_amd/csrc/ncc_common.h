@@ -1,10 +1,12 @@
 // Shared by the NCC sweep kernels (ncc.hip: scalar forms and the window
 // planes; ncc_mfma.hip: the matrix-core form): row-pair plane indexing, the
-// launch arguments, the LDS-DMA and the exact min / max / med3 helpers.
+// LDS-DMA and the exact min / max / med3 helpers.  The launch arguments and
+// every host-side decision are ncc_plan.h's.
 #pragma once
 #include <cstdint>
 #include <vector>
 #include "mvs_internal.h"
+#include "ncc_plan.h"  // NccArgs, the parity modes, NccLaunch
 
 namespace mvs {
 namespace ncc {
@@ -16,21 +18,7 @@ __host__ __device__ __forceinline__ long pair_index(int y, int x, int W) {
   return (((long)(y >> 1) * W + x) << 1) + (y & 1);
 }
 
-constexpr int kMaxNbr = 16;
-constexpr int kMaxRef = 8;  // reference views per launch (the fused sweep takes a run of them)
 constexpr int kCPolNT = 2;  // buffer cache policy: non-temporal (CPol::NT on gfx940+)
-struct NccArgs {
-  int W, H, D, nref;
-  int tiles_x, ntiles, tiles_per_xcd, nch;  // XCD-aware work map over nref x ntiles tiles (see k_ncc_volume)
-  int pk_pairs, st_pairs;  // LDS band heights in row pairs; the pair-row stride is the template BW
-  int txmax_all;           // (matrix-core runs) the largest band origin shift of any step: tiles with
-                           // x0 >= it never hold image column -1 in a band
-  int plane32;             // (scalar kernels) a view plane is under 2 GB: band DMA by buffer descriptors
-  // per reference view r of the launch: view id, neighbour count, first plan
-  // record, neighbour view ids
-  int z[kMaxRef], nn[kMaxRef], plan[kMaxRef];
-  int view[kMaxRef][kMaxNbr];
-};
 // host-built plan (device memory, cached per context): one 128-B record per
 // (chunk c, neighbour n, wave w), read with one scalar load per neighbour.
 // A __restrict__ kernel parameter, so the loads are SMEM and never wait on
@@ -41,6 +29,7 @@ struct alignas(128) NccRec {
   int lv[16];        // per level j of wave w: {txmax - tx, pk start row | stats start row << 16 (band-relative)}
   int pad[12];
 };
+static_assert(sizeof(NccRec) == 4 * kRecWords, "the planner writes 32-word records");
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -96,14 +85,6 @@ constexpr float kWtaInit = 1000000.0f;  // k_wta's Top4 initial cost (sweep.hip)
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Row-parity modes of a launch's bands (k_ncc_volume's PAR; the plan knows it):
-//   kParEven  every level's pk and stats rows start on a pair boundary (K = 5
-//             with horizontal neighbours: R + tymax even)
-//   kParOdd   every pk start is odd and every stats start even (K = 7 with
-//             horizontal neighbours: R = 3)
-//   kParMixed either, per level (vertical / diagonal neighbours): a run-time test
-constexpr int kParMixed = 0, kParEven = 1, kParOdd = 2;
 
 // N consecutive band rows starting at band row r0 of a row-pair band (pair
 // row stride BW, one column): ds_read_b128 per pair; an odd start takes the
@@ -213,23 +194,18 @@ __device__ __forceinline__ int dot4(unsigned a, unsigned b, int c) {
   return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }
 
-// the matrix-core fused sweep (ncc_mfma.hip): its plan (one 128-B record per
-// chunk of 16 NDB levels and neighbour) and one launch over a run of
-// reference views.  vert: some neighbour shifts rows (the general form:
-// per-level band rows, pair reads split at odd offsets); NB: band buffers
-struct NccPlanM {
-  std::vector<int32_t> table;
-  int band_w = 0;                // columns per band pair row: 64 + the widest chunk span
-  int pk_pairs = 0, st_pairs = 0;  // band heights in row pairs (the tallest step)
-  int ndb = 2;                   // 16-level blocks per chunk
-  bool vert = false;
+// One planned launch (ncc_plan.h) with its device pointers: ncc.hip and
+// ncc_mfma.hip each map it to the kernel instantiation of its coordinates.
+struct NccCall {
+  mvs_ctx* ctx;
+  const NccLaunch& L;
+  const uint2 *stats, *pk;
+  const int32_t* plan;  // L.table on the device
+  float* vol;           // the cost volume, or null: the fused sweep into wo
+  WtaOut wo;
 };
-NccPlanM make_plan_mfma(const float* levels, int D, int nn, const float* fdx, const float* fdy, float bl, int ndb,
-                        int K = 5);
-// the LDS bytes of one workgroup of the matrix-core form
-size_t mfma_lds_bytes(const NccPlanM& p, int band_w, int nb, int tmax, int D);
-int launch_ncc_mfma(mvs_ctx* ctx, const uint2* stats, const uint2* pk, const int32_t* plan_dev, NccArgs& a,
-                    const WtaOut& wo, int bw, int tmax, bool vert, int ndb, int nb, int K);
+inline int no_kernel() { return arg_fail("NCC sweep: no kernel instantiation for the planned launch"); }
+int launch_ncc_mfma(const NccCall& c);  // the matrix-core family (ncc_mfma.hip)
 
 }  // namespace ncc
 }  // namespace mvs

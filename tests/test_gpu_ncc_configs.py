@@ -296,6 +296,42 @@ def test_ncc_wta_range(eng, case):
     same(nd, rd, "range without confidence")
 
 
+def test_launches_match_the_planner_golden(eng, monkeypatch):
+    """The launcher runs what the planner's golden says (tests/test_ncc_plan_cpu.py,
+    case grid3x3: a 3 x 3 array, 8-neighbour lists, 128 x 32, 48 levels): one
+    fused sweep over all nine views makes as many kernel launches as the case
+    has lines (two: eight views, then one), the last launch reports the last
+    line's variant slots, and the maps are the oracle's."""
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ncc_launch_plans.txt")
+    with open(golden) as f:
+        text = f.read()
+    lines = text.split("== grid3x3\n", 1)[1].split("== ", 1)[0].splitlines()
+    assert len(lines) == 2 and all(" launch " in ln for ln in lines), lines
+    for k in [k for k in os.environ if k.startswith("MVS_NCC_")]:
+        monkeypatch.delenv(k)
+    aw, ah, W, H, dmax, K = 3, 3, 128, 32, 47, 5
+    stack, _ = synth.make_stack(W, H, aw, ah, 0, dmax, 1.0, 0x5EED + 11)
+    cam = _array(aw, ah, 0, dmax, nh=1, nv=1)
+    lab, l8 = eng.cvt(torch.from_numpy(stack).cuda())
+    box = eng.box_stats(l8, K)
+    eng.set_kernel_timing(True)
+    try:
+        rd, rc = eng.ncc_wta_range(l8, box, cam, 0, aw * ah, K)
+        times = eng.kernel_times()
+    finally:
+        eng.set_kernel_timing(False)
+    assert len(times) == len(lines), (times, lines)
+    last = [int(v) for v in lines[-1].rsplit("last=", 1)[1].split(",")]
+    assert list(eng.ncc_last_variant().values()) == last
+    l8h = l8.cpu().numpy()
+    for z in range(aw * ah):
+        want = orc.ncc_volume(l8h, cam.levels, cam.view_subset, cam.subset_num, aw, 1.0, K, z)
+        od, oc = orc.wta(want, cam.levels)
+        same(rd[z], od, f"disp z{z}")
+        same(rc[z], oc, f"conf z{z}")
+
+
 @pytest.mark.parametrize("bl", [1.0, 1.0359])
 def test_sweep_spixl_transposed_vertical(engine, monkeypatch, bl):
     """The superpixel sweep reads vertical neighbours (same camera column) from
