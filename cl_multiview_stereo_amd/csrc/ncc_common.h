@@ -61,6 +61,22 @@ __device__ __forceinline__ float vmin3(float a, float b, float c) {
   asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
+__device__ __forceinline__ unsigned vmin3u(unsigned a, unsigned b, unsigned c) {
+  unsigned r;
+  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+// the smallest of 16 as a tree of seven min3 and one min (v_min_f32's NaN rule: dropped)
+__device__ __forceinline__ float vmin16(const float (&v)[16]) {
+  const float a0 = vmin3(v[0], v[1], v[2]), a1 = vmin3(v[3], v[4], v[5]), a2 = vmin3(v[6], v[7], v[8]);
+  const float a3 = vmin3(v[9], v[10], v[11]), a4 = vmin3(v[12], v[13], v[14]);
+  return vmin(vmin3(a0, a1, a2), vmin3(a3, a4, v[15]));
+}
+__device__ __forceinline__ unsigned vmin16u(const unsigned (&v)[16]) {
+  const unsigned a0 = vmin3u(v[0], v[1], v[2]), a1 = vmin3u(v[3], v[4], v[5]), a2 = vmin3u(v[6], v[7], v[8]);
+  const unsigned a3 = vmin3u(v[9], v[10], v[11]), a4 = vmin3u(v[12], v[13], v[14]);
+  return min(vmin3u(a0, a1, a2), vmin3u(a3, a4, v[15]));
+}
 // IEEE 754-2019 maximum of three (gfx950): NaN when any operand is NaN
 __device__ __forceinline__ float vmaximum3(float a, float b, float c) {
   float r;

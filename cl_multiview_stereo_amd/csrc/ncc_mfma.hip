@@ -216,15 +216,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     stage(0, 0, 0);
   }
   const long zo = (long)a.z[ref] * Pv;
+  // The reference plane's rows this tile reads (the window rows of its pixels,
+  // the blocks' footprints) lie within 8 pair rows of pair zp0, so they are
+  // read through one buffer descriptor based there: a row is a scalar offset,
+  // a column a 32-bit lane offset, no per-lane 64-bit address arithmetic.
+  const int zp0 = min(max((y0 >> 1) - (K == 5 ? 1 : 2), 0), Hp2 - 1);
+  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)((const char*)pk + 8 * (zo + 2L * W * zp0)), 0, 16 * W * min(Hp2 - zp0, 8), 0x00020000);
   // -Sr' and s_r of the tile's 64 x TH pixels (lane = column), as k_ncc_volume:
   // wave w takes rows w, w + 8, ... (one correctly rounded sqrt + divide per
   // row and lane, spread over the waves instead of TH of them on wave 0)
   for (int o = wave; o < TH; o += NW) {
-    const int x = x0 + lane, xc = min(x, W - 1), y = y0 + o;
+    const int x = x0 + lane, y = y0 + o;
+    const int xoff = 16 * min(x, W - 1);
     int s1 = 0, s2 = 0;
 #pragma unroll
     for (int k = 0; k < 2 * R + 1; k++) {
-      const uint2 v = pk[zo + pair_index(min(max(y - R + k, 0), H - 1), xc, W)];
+      const int yc = min(max(y - R + k, 0), H - 1);  // (wave-uniform: the row's offset is scalar)
+      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rz, xoff, 16 * W * ((yc >> 1) - zp0) + 8 * (yc & 1), 0);
       const unsigned lo = v.x, hi = v.y & (K == 5 ? 0xffu : 0xffffffu);  // the window's K bytes
       s1 = dot4(lo, 0x01010101u, dot4(hi, 0x01010101u, s1));
       s2 = dot4(lo, lo, dot4(hi, hi, s2));
@@ -246,34 +255,42 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
   {
     const int mA = lane & 15, g = lane >> 4;
     const int xxA = K == 5 ? mA >> 2 : mA >> 3, yyA = K == 5 ? mA & 3 : mA & 7;
+    // a row's 8 bytes masked to the window's K columns: K bytes of ones moved
+    // xxA bytes up; a footprint row rr = 2 (g + 4 mf) + h outside the window's
+    // rows (K = 5: yyA .. yyA + 4; K = 7: yyA + 1 .. yyA + 7) takes no tap
+    const unsigned long long cm = (K == 5 ? 0xFFFFFFFFFFull : 0xFFFFFFFFFFFFFFull) << (8 * xxA);
+    const unsigned cm_lo = (unsigned)cm, cm_hi = (unsigned)(cm >> 32);
     unsigned msk[MF][4];
 #pragma unroll
     for (int mf = 0; mf < MF; mf++)
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int h = k >> 1, rr = 2 * (g + 4 * mf) + h;
-        unsigned mk = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-          const int t = 4 * (k & 1) + b;
-          const bool in = K == 5 ? (t >= xxA && t <= xxA + 4 && rr >= yyA && rr <= yyA + 4)
-                                 : (t >= xxA && t <= xxA + 6 && rr >= yyA + 1 && rr <= yyA + 7);
-          if (in) mk |= 0xffu << (8 * b);
-        }
-        msk[mf][k] = mk;
+      for (int h = 0; h < 2; h++) {
+        const int rr = 2 * (g + 4 * mf) + h;
+        const bool in = (unsigned)(rr - yyA - (K == 5 ? 0 : 1)) <= (unsigned)(K - 1);
+        msk[mf][2 * h] = in ? cm_lo : 0u;
+        msk[mf][2 * h + 1] = in ? cm_hi : 0u;
       }
+    // the entries: the lane's pair row as one 32-bit offset per (yb | mf), the
+    // block's column (wave-uniform) as the load's scalar offset
+    constexpr int NPR = K == 5 ? NYB : MF;
+    int roff[NPR];
 #pragma unroll
-    for (int xb = 0; xb < XB; xb++)
+    for (int i = 0; i < NPR; i++) {
+      const int pr = min(max((K == 5 ? (y0 >> 1) - 1 + 2 * i : (y0 >> 1) - 2 + 4 * i) + g, 0), Hp2 - 1);
+      roff[i] = 16 * W * (pr - zp0);
+    }
+#pragma unroll
+    for (int xb = 0; xb < XB; xb++) {
+      const int xcol = min(x0 + 8 * wave + BXW * xb, W - 1);
 #pragma unroll
       for (int yb = 0; yb < NYB; yb++)
 #pragma unroll
         for (int mf = 0; mf < MF; mf++) {
-          const int xcol = min(x0 + 8 * wave + BXW * xb, W - 1);
-          const int pr = min(max(K == 5 ? (y0 >> 1) - 1 + 2 * yb + g : (y0 >> 1) - 2 + g + 4 * mf, 0), Hp2 - 1);
-          const u32x4 v = *(const u32x4*)(pk + zo + (((long)pr * W + xcol) << 1));
+          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rz, roff[K == 5 ? yb : mf], 16 * xcol, 0);
           A[xb * NYB + yb][mf] = i32x4{(int)(v.x & msk[mf][0]), (int)(v.y & msk[mf][1]), (int)(v.z & msk[mf][2]),
                                        (int)(v.w & msk[mf][3])};
         }
+    }
   }
   // this lane's output pixels of block (xb, yb): column 8 wave + pcol, rows
   // prow .. prow + 3 of the tile (the MFMA's C[4 (l >> 4) + r][l & 15])
@@ -560,23 +577,28 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
           for (int r = 0; r < 4; r++) {
             const int kb = xb * NYB + kyb;
             const int q = cls * kMfMergeStride + r * 64 + 8 * wave + pcol(xb, g);
+            // (0xffff, no level, goes as it is: above every level, D <= 65535)
             const unsigned v = (r & 1) ? wi0p[kb][r >> 1] >> 16 : wi0p[kb][r >> 1] & 0xffffu;
             m0[q] = wv0[kb][r];
             m1[q] = wv1[kb][r];
-            mi[q] = v == 0xffffu ? -1 : (int)v;
+            mi[q] = (int)v;
           }
       }
     }
     __syncthreads();
     if (tid < 256) {
       const int q = tid, xx = x0 + (q & 63), yy = y0 + 4 * yb + (q >> 6);
-      // lexicographic (cost, level) minimum; "no level" (-1) compares as the
-      // largest level (it only ever comes with the initial cost 1e6, which no
-      // real level has).  Costs can be slightly negative (NCC rounding past 1),
-      // so they are compared as floats.
+      // lexicographic (cost, level) minimum; "no level" (0xffff) compares as
+      // the largest level (it only ever comes with the initial costs 1e6, 1e6,
+      // which no real level has).  Costs can be slightly negative (NCC
+      // rounding past 1), so they are compared as floats.
       // every class's entries read up front (one LDS latency, not one per
-      // class), the minimum as a branch-free tree (the order is immaterial:
-      // the classes' levels are distinct, so no two entries tie in both keys)
+      // class).  The classes' levels are distinct, so no two entries tie in
+      // both keys and the minimum splits in two: the smallest cost as a min3
+      // tree, then the smallest level among the classes that hold that cost.
+      // The costs are never NaN (the fold's minima drop it) nor -0 (1 - m
+      // rounds an exact zero to +0), so == finds exactly the classes whose
+      // cost has bv's bits.
       float v0s[16], v1s[16];
       unsigned is[16];
 #pragma unroll
@@ -585,29 +607,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         is[w] = (unsigned)mi[w * kMfMergeStride + q];
         v1s[w] = m1[w * kMfMergeStride + q];
       }
-      float tv[16];
+      const float bv = vmin16(v0s);
       unsigned ti[16];
 #pragma unroll
-      for (int w = 0; w < 16; w++) {
-        tv[w] = v0s[w];
-        ti[w] = is[w];
-      }
+      for (int w = 0; w < 16; w++) ti[w] = v0s[w] == bv ? is[w] : 0xffffffffu;
+      const unsigned bi = vmin16u(ti);
+      // the second smallest outside bi +- 1: a class whose level lies there
+      // gives its own second smallest (both are <= the initial cost kWtaInit;
+      // a class with no level holds that cost twice, so its test is immaterial)
+      const unsigned bl = bi - 1u;
+      float sv[16];
 #pragma unroll
-      for (int h = 8; h >= 1; h >>= 1)
-#pragma unroll
-        for (int w = 0; w < h; w++) {
-          const bool tk = (tv[w + h] < tv[w]) | ((tv[w + h] == tv[w]) & (ti[w + h] < ti[w]));
-          tv[w] = tk ? tv[w + h] : tv[w];
-          ti[w] = tk ? ti[w + h] : ti[w];
-        }
-      const float bv = tv[0];
-      const unsigned bi = ti[0];
-      float c2 = kWtaInit;
-#pragma unroll
-      for (int w = 0; w < 16; w++) {
-        const float v = (unsigned)((int)is[w] - (int)bi + 1) <= 2u ? v1s[w] : v0s[w];
-        c2 = vmin(c2, v);
-      }
+      for (int w = 0; w < 16; w++) sv[w] = is[w] - bl <= 2u ? v1s[w] : v0s[w];
+      float c2 = vmin16(sv);
       // The fold skipped the clamp (cost = 1 - max(-1, m) = min(2, 1 - m)).
       // If the smallest cost is below 2 the clamp changes neither it nor its
       // level, and the second smallest outside bi +- 1 is min(2, that) whenever
