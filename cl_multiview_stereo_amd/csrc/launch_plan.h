@@ -1,0 +1,129 @@
+// The launch planners of the superpixel sweep, the per-pixel SAD sweep and the
+// view-consistency filter: every host-side decision of launch_sweep_spixl,
+// launch_sweep_pixel_sad and launch_remove_incons (kernel form, grids, the
+// re-layout slot table, the SAD step records, LDS bytes) as plain C++ with no
+// HIP header and no mvs_ctx, so it builds with g++ and runs without a GPU
+// (tests/host/launch_plan_check.cpp prints its decisions).  sweep.hip and
+// refine.hip map a plan to a kernel instantiation and launch it.  The structs
+// and constants below that a kernel reads too are defined here once.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace mvs {
+
+inline int map_dim(int n, int S) {
+  // (int)ceil((float)n / (float)S), pipeline.cpp:18-19
+  return (int)__builtin_ceilf((float)n / (float)S);
+}
+
+// ---- shared with k_sweep_spixl_ring (sweep.hip) ----------------------------
+constexpr int kSwU = 336;  // C5 (S = 40, |dx| <= 4): 78 + 2 + 252 = 332
+
+// ---- shared with k_sad_band / k_sweep_pixel_sad (sweep.hip) ----------------
+constexpr int SB_TW = 60;   // output columns per tile
+constexpr int SB_NBLK = 2;  // 64-column blocks per band row (band columns <= 128)
+struct SadArgs {
+  int W, H, D, nn, z;
+  int tiles_x, ntiles, tiles_per_xcd, nch;
+  int bw, brows;  // LDS band pitch (pixels) and rows per buffer
+};
+// host-built plan, one record per step (c, n), read by scalar loads
+struct alignas(16) SadRec {
+  int view, sxmin, sxmax, pad0;
+  float fdymin, fdymax;
+  int pad1[2];
+  int sx[16];     // per level j of the chunk: column shift d*dx (integral)
+  float fdy[16];  // per level j: (bl*d)*dy, the reference's float row shift
+};
+static_assert(sizeof(SadRec) == 160, "SadRec is uploaded as 40 int32 words");
+constexpr int PT = 32;           // output tile edge
+
+// ---- shared with k_remove_incons_q (refine.hip) ----------------------------
+constexpr int kFilterRG = 4;  // reference views per workgroup of the q kernel
+
+namespace plan {
+
+// Every knob of the three launchers.  plan_tuning() is the one place that
+// reads them, all of them per call.
+struct Tuning {
+  int sweep_wps = 0;        // MVS_SWEEP_WPS=1|2|4: another wave count per superpixel (0: automatic; ignored at D <= 32)
+  int sweep_transpose = 2;  // MVS_SWEEP_TRANSPOSE: 0 row-major gathers only, 1 vertical neighbours re-laid, 2 diagonal ones too
+  bool sweep_hz = true;     // MVS_SWEEP_HZ=0: the general form where HZ would run
+  bool sweep_ring = true;   // MVS_SWEEP_RING=0: the HZ gathers where the ring form would run
+  // MVS_SAD_KERNEL: "sys8x2", "sys8", "gather"; unset: 16-level chunks, else
+  // 8-level chunks (taller bands: vertical neighbours), else the gather kernel.
+  // A band variant named explicitly never falls back (MVS_E_UNSUPPORTED), so a
+  // test of it cannot pass on another.
+  std::string sad_kernel = "auto";
+  bool sad_named = false;    // MVS_SAD_KERNEL is set
+  bool sad_aff = true;       // MVS_SAD_AFF set (any value): the row-table path
+  bool filter_px = false;    // MVS_FILTER_KERNEL=px: the per-pixel form at 16 < V <= 32
+  int filter_fb_q = 2;       // MVS_FILTER_FB, views per gather block: the q kernel takes 4, else 2
+  int filter_fb_px = 4;      //   the px kernel takes 4 or 2, else 8 (its default is 4, q's is 2)
+  int filter_ns = 2;         // MVS_FILTER_NS: candidate slots per lane (1, else 2)
+  bool filter_bound = true;  // MVS_FILTER_BOUND=0: the walk's bounds over every view
+  bool filter_ref_order = false;  // MVS_FILTER_ORDER=ref: the q kernel's grid as (x tiles, rows, reference groups)
+};
+Tuning plan_tuning();
+
+// ---- launch_sweep_spixl -----------------------------------------------------
+// the form of a launch, as mvs_sweep_last_variant_n reports it
+constexpr int kSweepGeneral = 0, kSweepHzGather = 1, kSweepHzRing = 2, kSweepRelaid = 3;
+struct SpixlRelayout {
+  int view, kind, slot;  // k_relayout_lab<kind> of `view` to labT + slot * tstride
+};
+struct SpixlSweepPlan {
+  const char* err = nullptr;  // the argument error, if any
+  bool launch = false;        // false: nothing to do (an empty view range)
+  int form = 0, lps = 64, wps = 1;  // k_sweep_spixl<lps, form == relaid, form == HZ>(wps) or k_sweep_spixl_ring<wps>
+  int mw = 0, mh = 0;
+  unsigned grid_x = 0, grid_y = 0;
+  // re-laid neighbour views: slot[4 * view + kind] in units of tstride
+  // elements, -1 none (empty without re-laid views); the copies in launch order
+  std::vector<int32_t> slot;
+  std::vector<SpixlRelayout> relayouts;
+  long units = 0, tstride = 0;
+  int last[5] = {0, 0, 0, 0, 0};  // {FORM, LPS, WPS, TMODE, RELAID}
+};
+// vs, sn, levels: the host lists.  allow_relayout = false: the plan of the
+// same call without the re-layout scratch (it may then be HZ or ring).
+SpixlSweepPlan plan_sweep_spixl(const Tuning& t, int V, int W, int H, int S, int D, const float* levels,
+                                const int* vs, const int* sn, int aw, int z0, int z1, bool allow_relayout);
+
+// ---- launch_sweep_pixel_sad -------------------------------------------------
+struct SadPlan {
+  bool band = false;  // k_sad_band<TH, PPW, AFF, BWT>, else k_sweep_pixel_sad
+  int TH = 0, PPW = 0, AFF = 0, BWT = 0;
+  std::vector<int32_t> table;  // the SadRec of every step (c, n)
+  SadArgs args{};
+  size_t lds = 0;
+  unsigned grid_x = 0, grid_y = 1;
+  std::string err;  // MVS_E_UNSUPPORTED: a named variant cannot stage this geometry
+};
+// The band form of DC = 8 PPW levels per step and RR = TH + 4 region rows for
+// reference view z: false when the level set has fractional column shifts or
+// the bands do not fit the LDS; else p's table, args (the work map included),
+// lds, AFF and BWT are filled.
+bool sad_band_geometry(int DC, int RR, bool aff, int V, int W, int H, int D, const float* levels, const int* vs,
+                       const int* sn, int aw, float bl, int z, SadPlan& p);
+SadPlan plan_sad(const Tuning& t, int V, int W, int H, int D, const float* levels, const int* vs, const int* sn,
+                 int aw, float bl, int z);
+
+// ---- launch_remove_incons ---------------------------------------------------
+enum FilterKernel { kFilterNone, kFilterSel8, kFilterPx16_8, kFilterQ, kFilterPx32, kFilterSel64, kFilterPlain };
+struct FilterPlan {
+  FilterKernel kernel = kFilterNone;  // none: no rows or no views
+  int FB = 0, NS = 0, ROWB = 0, RM = 0;  // q: k_remove_incons_q<kFilterRG, FB, NS, ROWB, RM>; px32: FB
+  int inb = 0;                           // q: the walk's bounds from the array's rows
+  unsigned grid[3] = {0, 1, 1}, block = 256;
+  long PP = 0;        // proj's view stride in elements
+  long proj_off = 0;  // added to proj: a band holds rows [ya, yb) only
+};
+FilterPlan plan_remove_incons(const Tuning& t, int V, int W, int H, int aw, int z0, int z1, int ya, int yb,
+                              bool band);
+
+}  // namespace plan
+}  // namespace mvs

@@ -13,6 +13,7 @@
 
 #include "../../include/mvs.h"
 #include "../../include/mvs_detmath.h"
+#include "launch_plan.h"  // map_dim, and what the sweep / SAD / filter kernels share with their planners
 
 struct mvs_ctx {
   int device = 0;
@@ -84,11 +85,6 @@ int arg_fail(const char* what);
 void* scratch(mvs_ctx* ctx, size_t bytes, int* rc);
 const int32_t* plan_upload(mvs_ctx* ctx, const std::vector<int32_t>& table, int* rc);
 
-inline int map_dim(int n, int S) {
-  // (int)ceil((float)n / (float)S), pipeline.cpp:18-19
-  return (int)__builtin_ceilf((float)n / (float)S);
-}
-
 constexpr int kLocal = 16;  // LOCAL_SIZE_UPDATE, header.h:37-38
 
 #define MVS_LAUNCH_CHECK(what)                          \
@@ -121,6 +117,9 @@ int launch_suppress(hipStream_t s, const uint32_t* in, uint32_t* out, int V, int
 
 int launch_boundary(hipStream_t s, int V, int W, int H, int S, const float* spixl, const uint32_t* labels,
                     uint8_t* rep);
+// launch_sweep_spixl, launch_sweep_pixel_sad and launch_remove_incons decide
+// nothing themselves: launch_plan.cpp plans (kernel form, grids, tables, LDS),
+// they upload the tables and map the plan to a kernel instantiation
 int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* lab, float* spixl,
                        const uint8_t* rep, const float* levels, int D, const int* vs, const int* sn, int aw,
                        float bl, int z0, int z1);

@@ -1469,96 +1469,58 @@ int launch_proj_inv(hipStream_t s, int V, int W, int H, int aw, float bl, const 
   return 0;
 }
 
+namespace {
+// k_remove_incons_q by plan coordinates: index 8 (NS == 2) + 4 (FB == 2) + 2 !ROWB + !RM.  (The tables of
+// launch_remove_incons name their kernels in the order the launcher has always instantiated them in, which
+// is the order the code object holds them in.)
+using FilterQKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
+                               long, int);
+using FilterPxKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
+                                long);
+template <int I>
+constexpr FilterQKernel filter_q =
+    k_remove_incons_q<kFilterRG, (I & 4) ? 2 : 4, (I & 8) ? 2 : 1, (I & 2) == 0, (I & 1) == 0>;
+}  // namespace
+
 // remove_view_inconsistency for reference views [z0, z1): reads every proj
-// slice (all V must be filled) and the full disparity stack
+// slice (all V must be filled) and the full disparity stack.  The kernel, its
+// grid and proj's addressing are plan_remove_incons's (launch_plan.cpp).
 int launch_remove_incons(hipStream_t s, int V, int W, int H, int aw, float bl, float fuse, const float* full,
                          const float* proj, float* out, int z0, int z1, int ya, int yb, bool band) {
-  const int NR = yb - ya;  // rows [ya, yb) only (the caller checks 0 <= ya <= yb <= H)
-  // band: proj holds rows [ya, yb) only, as [V][yb - ya][W] (the kernels index
-  // proj[PP * view + y * W + x], so the band's base moves up by ya rows)
-  const long PP = band ? (long)NR * W : (long)W * H;
-  if (band) proj -= (long)ya * W;
-  if (z1 > z0 && NR > 0) {
-    const dim3 g((W + 255) / 256, NR, z1 - z0);
-    const dim3 gp((W + 255) / 256, NR);
-    // few views: one thread per (reference, pixel) keeps more threads in flight
-    // (measured at V = 5: 350 vs 395 us); many views: one thread per pixel
-    const bool off32 = (long)V * W * H * 4 < (1L << 31);  // 32-bit gather offsets (the sel / q kernels)
-    if (V <= 8 && off32)
-      hipLaunchKernelGGL(k_remove_incons_sel<8>, g, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
-    else if (V <= 16)
-      hipLaunchKernelGGL((k_remove_incons_px<16, 8>), gp, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0, z1,
-                         out, ya, PP);
-    else if (V <= 32 && (long)V * W * H * 4 < (1L << 31) &&
-             !(getenv("MVS_FILTER_KERNEL") && std::string(getenv("MVS_FILTER_KERNEL")) == "px")) {
-      // 32-bit gather offsets: one work queue per lane (k_remove_incons_q,
-      // MVS_FILTER_NS candidates at once, MVS_FILTER_FB views per gather block,
-      // both read per call); MVS_FILTER_KERNEL=px: the per-pixel form below.
-      // Measured at C4, all 32 references with k_proj_inv
-      // (scripts/bench_filter.py): q 18.1 ms (NS 2, FB 2); the lane-balanced
-      // hand-out of (pixel, candidate) items 21.1 ms and the lock-step walk
-      // 27.9 ms (both removed in round 3).
-      constexpr int RG = 4;
-      const dim3 gl((W + 63) / 64, NR, (z1 - z0 + RG - 1) / RG);
-      {
-        const char* fb = getenv("MVS_FILTER_FB");
-        const int nfb = fb ? atoi(fb) : 2;
-#define MVS_RIQ(FBV, NSV)                                                                                         \
-  if (aw % FBV == 0 && rmo)                                                                                       \
-    hipLaunchKernelGGL((k_remove_incons_q<RG, FBV, NSV, true, true>), glr, dim3(64 * RG), 0, s, proj, full, V, W, \
-                       H, aw, bl, fuse, z0, z1, out, ya, PP, inb);                                                        \
-  else if (aw % FBV == 0)                                                                                         \
-    hipLaunchKernelGGL((k_remove_incons_q<RG, FBV, NSV, true, false>), gl, dim3(64 * RG), 0, s, proj, full, V, W, \
-                       H, aw, bl, fuse, z0, z1, out, ya, PP, inb);                                                        \
-  else if (rmo)                                                                                                   \
-    hipLaunchKernelGGL((k_remove_incons_q<RG, FBV, NSV, false, true>), glr, dim3(64 * RG), 0, s, proj, full, V,   \
-                       W, H, aw, bl, fuse, z0, z1, out, ya, PP, inb);                                                     \
-  else                                                                                                            \
-    hipLaunchKernelGGL((k_remove_incons_q<RG, FBV, NSV, false, false>), gl, dim3(64 * RG), 0, s, proj, full, V,   \
-                       W, H, aw, bl, fuse, z0, z1, out, ya, PP, inb);
-        // MVS_FILTER_BOUND=0 (read per call): the walk's bounds over every view (A/B)
-        const char* fbd = getenv("MVS_FILTER_BOUND");
-        const int inb = (V % aw == 0 && !(fbd && atoi(fbd) == 0)) ? 1 : 0;
-        const bool rmo = !(getenv("MVS_FILTER_ORDER") && std::string(getenv("MVS_FILTER_ORDER")) == "ref");
-        const dim3 glr(((W + 63) / 64) * ((z1 - z0 + RG - 1) / RG), NR);
-        const char* ns = getenv("MVS_FILTER_NS");  // candidate slots per lane (1 | 2)
-        const int nns = ns ? atoi(ns) : 2;
-        if (nns == 1) {
-          if (nfb == 4) {
-            MVS_RIQ(4, 1)
-          } else {
-            MVS_RIQ(2, 1)
-          }
-        } else if (nfb == 4) {
-          MVS_RIQ(4, 2)
-        } else {
-          MVS_RIQ(2, 2)
-        }
-#undef MVS_RIQ
-      }
-    } else if (V <= 32) {
-      // MVS_FILTER_FB: views per gather block (A/B; read per call).  Measured at
-      // C4 (scripts/bench_filter.py): blocks of 8 gathers 54 ms for all 32
-      // references, 4: 35 ms, 2: 35 ms -- a candidate's early exit comes after
-      // ~3 gathers, so 8-wide blocks fetched twice what the vote needed
-      const char* fb = getenv("MVS_FILTER_FB");
-      const int nfb = fb ? atoi(fb) : 4;
-      if (nfb == 4)
-        hipLaunchKernelGGL((k_remove_incons_px<32, 4>), gp, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0,
-                           z1, out, ya, PP);
-      else if (nfb == 2)
-        hipLaunchKernelGGL((k_remove_incons_px<32, 2>), gp, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0,
-                           z1, out, ya, PP);
-      else
-        hipLaunchKernelGGL((k_remove_incons_px<32, 8>), gp, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0,
-                           z1, out, ya, PP);
+  const plan::FilterPlan p = plan::plan_remove_incons(plan::plan_tuning(), V, W, H, aw, z0, z1, ya, yb, band);
+  if (p.kernel == plan::kFilterNone) return 0;
+  const dim3 g(p.grid[0], p.grid[1], p.grid[2]), b(p.block);
+  proj += p.proj_off;
+  const long PP = p.PP;
+  switch (p.kernel) {
+    case plan::kFilterSel8:
+      hipLaunchKernelGGL(k_remove_incons_sel<8>, g, b, 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
+      break;
+    case plan::kFilterPx16_8:
+      hipLaunchKernelGGL((k_remove_incons_px<16, 8>), g, b, 0, s, proj, full, V, W, H, aw, bl, fuse, z0, z1, out, ya, PP);
+      break;
+    case plan::kFilterQ: {
+      static constexpr FilterQKernel q[16] = {
+          filter_q<0>, filter_q<1>, filter_q<2>,  filter_q<3>,  filter_q<4>,  filter_q<5>,  filter_q<6>,  filter_q<7>,
+          filter_q<8>, filter_q<9>, filter_q<10>, filter_q<11>, filter_q<12>, filter_q<13>, filter_q<14>, filter_q<15>};
+      hipLaunchKernelGGL(q[8 * (p.NS == 2) + 4 * (p.FB == 2) + 2 * !p.ROWB + !p.RM], g, b, 0, s, proj, full, V, W, H, aw,
+                         bl, fuse, z0, z1, out, ya, PP, p.inb);
+      break;
     }
-    else if (V <= 64 && off32)
-      hipLaunchKernelGGL(k_remove_incons_sel<64>, g, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
-    else
-      hipLaunchKernelGGL(k_remove_incons, g, dim3(256), 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
-    MVS_LAUNCH_CHECK("k_remove_incons");
+    case plan::kFilterPx32: {
+      static constexpr FilterPxKernel px[3] = {k_remove_incons_px<32, 4>, k_remove_incons_px<32, 2>,
+                                               k_remove_incons_px<32, 8>};
+      hipLaunchKernelGGL(px[p.FB == 4 ? 0 : p.FB == 2 ? 1 : 2], g, b, 0, s, proj, full, V, W, H, aw, bl, fuse, z0, z1,
+                         out, ya, PP);
+      break;
+    }
+    case plan::kFilterSel64:
+      hipLaunchKernelGGL(k_remove_incons_sel<64>, g, b, 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
+      break;
+    default:
+      hipLaunchKernelGGL(k_remove_incons, g, b, 0, s, proj, full, V, W, H, aw, bl, fuse, z0, out, ya, PP);
   }
+  MVS_LAUNCH_CHECK("k_remove_incons");
   return 0;
 }
 

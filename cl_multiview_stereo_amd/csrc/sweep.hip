@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void k_sweep_spixl(const float4* __restrict__ 
 // are in.  The launcher takes this form only when every window fits kSwU
 // columns: 2 (S - 1) + 2 + |dx| x the levels' range over any 64 consecutive
 // levels (stx <= (S - 1) / 2), else the HZ gathers.
-constexpr int kSwU = 336;  // C5 (S = 40, |dx| <= 4): 78 + 2 + 252 = 332
+// (kSwU: launch_plan.h, shared with the planner)
 __device__ __forceinline__ void wait_vm(int n) {  // s_waitcnt vmcnt(n), n in [0, 6]
   switch (n) {
     case 0: __builtin_amdgcn_s_waitcnt(0x0f70); break;
@@ -563,26 +563,13 @@ __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restri
 // The per-level minimum over neighbours folds into a first-minimum WTA in
 // level order; the 4 waves' (cost, level) winners are merged
 // lexicographically at the end.
-constexpr int SB_TW = 60;   // output columns per tile
-constexpr int SB_NBLK = 2;  // 64-column blocks per band row (band columns <= 128)
+// (SB_TW, SB_NBLK, SadArgs and SadRec: launch_plan.h, shared with the planner)
 constexpr float SB_INIT = 1000000.0f;
 // row-table entry of a row outside the image: a valid entry (yp-by0)*bw - bx0
 // is negative on the band's first row whenever bx0 > 0, so no -1 sentinel
 constexpr int SB_NOROW = -0x40000000;
 
-struct SadArgs {
-  int W, H, D, nn, z;
-  int tiles_x, ntiles, tiles_per_xcd, nch;
-  int bw, brows;  // LDS band pitch (pixels) and rows per buffer
-};
-// host-built plan, one record per step (c, n), read by scalar loads
-struct alignas(16) SadRec {
-  int view, sxmin, sxmax, pad0;
-  float fdymin, fdymax;
-  int pad1[2];
-  int sx[16];     // per level j of the chunk: column shift d*dx (integral)
-  float fdy[16];  // per level j: (bl*d)*dy, the reference's float row shift
-};
+static_assert(sizeof(SadRec) == 160, "k_sad_band reads one 160-byte record per step");
 
 // the band of step record e for the tile at (x0, y0): every neighbour pixel a
 // valid tap of the region can project to at any level of the chunk
@@ -865,7 +852,7 @@ __global__ __launch_bounds__(256) void k_sad_band(const float4* __restrict__ lab
 }
 
 // ---- per-pixel SAD sweep (S=1 grid semantics of initial_depth_estimation_v2)
-constexpr int PT = 32;           // output tile edge
+// (PT, the output tile edge: launch_plan.h)
 constexpr int PR = PT + 4;       // region edge (2-pixel halo)
 constexpr int PREG = PR * PR;    // 1296 region pixels
 constexpr int PPT = (PREG + 255) / 256;  // region pixels per thread (6)
@@ -1067,251 +1054,103 @@ __global__ __launch_bounds__(256) void k_relayout_lab(const float4* __restrict__
   }
 }
 
+// The superpixel sweep of reference views [z0, z1) as plan_sweep_spixl
+// (launch_plan.cpp) lays it out.  If the re-layout scratch cannot be had, the
+// call is planned again without it (same results, slower gathers).
 int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* lab, float* spixl,
                        const uint8_t* rep, const float* levels, int D, const int* vs, const int* sn, int aw,
                        float bl, int z0, int z1) {
-  if (z1 <= z0) return 0;
-  // k_sweep_spixl's 32-bit byte offsets within a view (a re-laid one spans
-  // at most (W + H) H elements)
-  if ((long)(W + H) * H * 16 >= (1L << 31)) return arg_fail("superpixel sweep: image too large for 32-bit offsets");
+  const plan::Tuning t = plan::plan_tuning();
+  const auto planned = [&](bool relayout) {
+    return plan::plan_sweep_spixl(t, V, W, H, S, D, ctx->h_levels.data(), ctx->h_vs.data(), ctx->h_sn.data(), aw, z0,
+                                  z1, relayout);
+  };
+  plan::SpixlSweepPlan p = planned(true);
+  if (p.err) return arg_fail(p.err);
+  if (!p.launch) return 0;
   hipStream_t s = ctx->stream;
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  long M = (long)mw * mh;
-  int wps = (D + 63) / 64;
-  wps = wps >= 3 ? 4 : wps;  // waves per superpixel: 1, 2 or 4
-  // MVS_SWEEP_WPS=1|2|4 (read per call): another wave count per superpixel (A/B)
-  const char* we = getenv("MVS_SWEEP_WPS");
-  const int wps_env = (we && D > 32 && (atoi(we) == 1 || atoi(we) == 2 || atoi(we) == 4)) ? atoi(we) : 0;
-  if (wps_env) wps = wps_env;
-  const bool half = D <= 32;  // two superpixels per wave
-  const int spb = half ? 8 : 4 / wps;
-  SweepArgs a{V, W, H, mw, mh, D, aw, z0, bl};
-  const long nb = (M + spb - 1) / spb;
-  // the vertical and diagonal neighbours of the references, re-laid into the
-  // context scratch; MVS_SWEEP_TRANSPOSE (read per call) = 0: row-major
-  // gathers only, 1: vertical neighbours only, 2 (default): both (A/B)
-  // Slot offsets are in units of H elements (tstride = H): a transposed slot
-  // takes W units, a sheared one W + H - 1.  If the scratch cannot be had, the
-  // row-major kernel runs instead (same results, slower gathers).
   const float4* labT = nullptr;
   const int* tslot = nullptr;
-  const long tstride = H;
-  const char* te = getenv("MVS_SWEEP_TRANSPOSE");
-  const int tmode = te ? atoi(te) : 2;
-  int relaid = 0;  // (view, kind) copies built (the report of mvs_sweep_last_variant_n)
-  if (tmode > 0) {
-    std::vector<int32_t> slot(4 * (size_t)V, -1);
-    long units = 0;
-    int nslots = 0;
-    for (int z = z0; z < z1; z++)
-      for (int k = 0; k < ctx->h_sn[z]; k++) {
-        const int v = ctx->h_vs[(size_t)V * z + k];
-        if (v < 0 || v >= V) continue;
-        const int dx = v % aw - z % aw, dy = v / aw - z / aw;
-        const int kind = dx == 0 ? 1 : tmode < 2 ? 0 : dx == dy ? 2 : dx == -dy ? 3 : 0;
-        if (kind && slot[4 * v + kind] < 0 && units + W + H <= INT32_MAX) {
-          slot[4 * v + kind] = (int32_t)units;
-          units += kind == 1 ? W : W + H - 1;
-          nslots++;
-        }
-      }
-    if (units > 0) {
-      int rc = 0;
-      float4* buf = (float4*)scratch(ctx, (size_t)units * tstride * sizeof(float4), &rc);
-      if (rc == MVS_E_NOMEM) {
-        (void)hipGetLastError();  // the failed hipMalloc must not fail the next launch check
-        units = 0;
-      } else if (rc) {
-        return rc;
-      }
-      if (units > 0) tslot = plan_upload(ctx, slot, &rc);
+  if (p.units > 0) {
+    int rc = 0;
+    float4* buf = (float4*)scratch(ctx, (size_t)p.units * p.tstride * sizeof(float4), &rc);
+    if (rc == MVS_E_NOMEM) {
+      (void)hipGetLastError();  // the failed hipMalloc must not fail the next launch check
+      p = planned(false);
+    } else if (rc) {
+      return rc;
+    } else {
+      tslot = plan_upload(ctx, p.slot, &rc);
       if (rc) return rc;
+      labT = buf;
       const dim3 tg((W + 31) / 32, (H + 31) / 32);
-      for (int v = 0; v < V && units > 0; v++)
-        for (int kind = 1; kind < 4; kind++) {
-          const int sl = slot[4 * v + kind];
-          if (sl < 0) continue;
-          float4* o = buf + (long)sl * tstride;
-          if (kind == 1)
-            hipLaunchKernelGGL(k_relayout_lab<1>, tg, dim3(256), 0, s, (const float4*)lab, W, H, v, o);
-          else if (kind == 2)
-            hipLaunchKernelGGL(k_relayout_lab<2>, tg, dim3(256), 0, s, (const float4*)lab, W, H, v, o);
-          else
-            hipLaunchKernelGGL(k_relayout_lab<3>, tg, dim3(256), 0, s, (const float4*)lab, W, H, v, o);
-        }
+      static constexpr void (*relayout[3])(const float4*, int, int, int, float4*) = {k_relayout_lab<1>, k_relayout_lab<2>,
+                                                                                     k_relayout_lab<3>};
+      for (const plan::SpixlRelayout& r : p.relayouts)
+        hipLaunchKernelGGL(relayout[r.kind - 1], tg, dim3(256), 0, s, (const float4*)lab, W, H, r.view,
+                           buf + (long)r.slot * p.tstride);
       MVS_LAUNCH_CHECK("k_relayout_lab");
-      if (units > 0) {
-        labT = buf;
-        relaid = nslots;
-      }
     }
   }
-  // HZ: every neighbour of [z0, z1) in the reference's camera row and every
-  // level x column offset an integer of magnitude below 2^24 (MVS_SWEEP_HZ=0,
-  // read per call: the general form, A/B)
-  bool hz = !labT && (long)W * H * 16 < (1L << 31) && !(getenv("MVS_SWEEP_HZ") && atoi(getenv("MVS_SWEEP_HZ")) == 0);
-  for (int z = z0; z < z1 && hz; z++)
-    for (int k = 0; k < ctx->h_sn[z] && hz; k++) {
-      const int v = ctx->h_vs[(size_t)V * z + k];
-      if (v / aw != z / aw) hz = false;
-      const float fdxv = (float)(v % aw - z % aw);
-      for (int l = 0; l < D && hz; l++) {
-        const float f = ctx->h_levels[l] * fdxv;  // the kernel's d * (float)(vx - rx)
-        if (!(fabsf(f) < 16777216.0f) || f != truncf(f)) hz = false;
-      }
-    }
-  // HZ with 64 levels per wave: the LDS-staged rows (MVS_SWEEP_RING=0, read per call: the gathers)
-  const char* re = getenv("MVS_SWEEP_RING");
-  bool ring_ok = hz && !half && !(re && atoi(re) == 0);
-  if (ring_ok) {  // every staged window fits kSwU columns (see k_sweep_spixl_ring)
-    float rng = 0.0f;
-    for (int c0 = 0; c0 < D; c0 += 64) {
-      float lo = ctx->h_levels[c0], hi = lo;
-      for (int l = c0; l < std::min(D, c0 + 64); l++) {
-        lo = std::min(lo, ctx->h_levels[l]);
-        hi = std::max(hi, ctx->h_levels[l]);
-      }
-      rng = std::max(rng, hi - lo);
-    }
-    int mdx = 0;
-    for (int z = z0; z < z1; z++)
-      for (int k = 0; k < ctx->h_sn[z]; k++) mdx = std::max(mdx, std::abs(ctx->h_vs[(size_t)V * z + k] % aw - z % aw));
-    if (2.0 * (S - 1) + 2.0 + (double)rng * mdx + 1.0 > (double)kSwU) ring_ok = false;
-  }
-  if (ring_ok) {
-    // one wave per superpixel, its 64-level passes in turn: the ring form's
-    // cost is per staged row and level, not per wave, and four superpixels per
-    // workgroup share its setup and tail (C5, D = 256: 1.19 ms per launch
-    // against 1.42 with four waves per superpixel; C2 alike at 1 and 2:
-    // profiles/r06/sweep_ring_waves.txt)
-    const int rw = wps_env ? wps_env : 1;
-    const long nbr = (M + 4 / rw - 1) / (4 / rw);
-    const dim3 g((unsigned)(8 * ((nbr + 7) / 8)), (unsigned)(z1 - z0));
-    if (rw == 1)
-      hipLaunchKernelGGL(k_sweep_spixl_ring<1>, g, dim3(256), 0, s, (const float4*)lab, spixl, rep, levels, vs, sn, a);
-    else if (rw == 2)
-      hipLaunchKernelGGL(k_sweep_spixl_ring<2>, g, dim3(256), 0, s, (const float4*)lab, spixl, rep, levels, vs, sn, a);
-    else
-      hipLaunchKernelGGL(k_sweep_spixl_ring<4>, g, dim3(256), 0, s, (const float4*)lab, spixl, rep, levels, vs, sn, a);
+  SweepArgs a{V, W, H, p.mw, p.mh, D, aw, z0, bl};
+  const dim3 g(p.grid_x, p.grid_y);
+  if (p.form == plan::kSweepHzRing) {
+    static constexpr void (*ring[3])(const float4*, float*, const uint8_t*, const float*, const int*, const int*,
+                                     SweepArgs) = {k_sweep_spixl_ring<1>, k_sweep_spixl_ring<2>, k_sweep_spixl_ring<4>};
+    hipLaunchKernelGGL(ring[p.wps == 1 ? 0 : p.wps == 2 ? 1 : 2], g, dim3(256), 0, s, (const float4*)lab, spixl, rep,
+                       levels, vs, sn, a);
     MVS_LAUNCH_CHECK("k_sweep_spixl_ring");
-    const int last[5] = {2, 64, rw, tmode, relaid};
-    std::copy(last, last + 5, ctx->sweep_last);
-    return 0;
+  } else {
+    const bool half = p.lps == 32;
+    const auto kern = p.form == plan::kSweepRelaid     ? (half ? k_sweep_spixl<32, true> : k_sweep_spixl<64, true>)
+                      : p.form == plan::kSweepHzGather ? (half ? k_sweep_spixl<32, false, true> : k_sweep_spixl<64, false, true>)
+                                                       : (half ? k_sweep_spixl<32, false> : k_sweep_spixl<64, false>);
+    hipLaunchKernelGGL(kern, g, dim3(256), 0, s, (const float4*)lab, spixl, rep, levels, vs, sn, a, p.wps, labT, tslot,
+                       p.tstride);
+    MVS_LAUNCH_CHECK("k_sweep_spixl");
   }
-  auto kern = labT ? (half ? k_sweep_spixl<32, true> : k_sweep_spixl<64, true>)
-              : hz ? (half ? k_sweep_spixl<32, false, true> : k_sweep_spixl<64, false, true>)
-                   : (half ? k_sweep_spixl<32, false> : k_sweep_spixl<64, false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(8 * ((nb + 7) / 8)), (unsigned)(z1 - z0)), dim3(256), 0, s,
-                     (const float4*)lab, spixl, rep, levels, vs, sn, a, wps, labT, tslot, tstride);
-  MVS_LAUNCH_CHECK("k_sweep_spixl");
-  const int last[5] = {labT ? 3 : hz ? 1 : 0, half ? 32 : 64, half ? 1 : wps, tmode, relaid};
-  std::copy(last, last + 5, ctx->sweep_last);
+  std::copy(p.last, p.last + 5, ctx->sweep_last);
   return 0;
 }
 
 namespace {
-// Band-staged SAD sweep: host plan + launch for one reference view.  Returns 1
-// when the level set has fractional column shifts or the bands do not fit
-// the LDS (the caller then uses k_sweep_pixel_sad).
-template <int TH, int PPW>
-int launch_sad_band_t(mvs_ctx* ctx, int V, int W, int H, const float* lab, const float* levels_host, int D,
-                      const int* vs_host, const int* sn_host, int aw, float bl, int z, float* disp) {
-  bool aff = getenv("MVS_SAD_AFF") == nullptr;  // MVS_SAD_AFF set: the row-table path (A/B)
-  constexpr int RR = TH + 4, DC = 8 * PPW;
-  const int nn = sn_host[z];
-  const int nch = (D + DC - 1) / DC;
-  const int rx = z % aw, ry = z / aw;
-  constexpr int RW = sizeof(SadRec) / 4;
-  std::vector<int32_t> table((size_t)std::max(1, nch * nn) * RW, 0);
-  int span_x = 0;
-  float span_y = 0.0f;
-  for (int c = 0; c < nch; c++)
-    for (int n = 0; n < nn; n++) {
-      SadRec e{};
-      const int view = vs_host[V * z + n];
-      const int dx = view % aw - rx, dy = view / aw - ry;
-      e.view = view;
-      e.sxmin = 1 << 30;
-      e.sxmax = -(1 << 30);
-      e.fdymin = INFINITY;
-      e.fdymax = -INFINITY;
-      for (int j = 0; j < DC; j++) {
-        const int dl = std::min(c * DC + j, D - 1);  // past the end: the last level (rows masked)
-        const float d = levels_host[dl];
-        const float fdx = d * (float)dx;  // the reference's float shifts (clcode.cl:1033-1034)
-        const float fdy = (bl * d) * (float)dy;
-        if (fdx != std::trunc(fdx) || std::fabs(fdx) > 1e6f) return 1;
-        e.sx[j] = (int)fdx;
-        e.fdy[j] = fdy;
-        if (fdy != std::trunc(fdy) || std::fabs(fdy) > 1e6f) aff = false;
-        if (c * DC + j < D) {
-          e.sxmin = std::min(e.sxmin, e.sx[j]);
-          e.sxmax = std::max(e.sxmax, e.sx[j]);
-          e.fdymin = std::min(e.fdymin, fdy);
-          e.fdymax = std::max(e.fdymax, fdy);
-        }
-      }
-      span_x = std::max(span_x, e.sxmax - e.sxmin);
-      span_y = std::max(span_y, e.fdymax - e.fdymin);
-      std::memcpy(table.data() + ((size_t)c * nn + n) * RW, &e, sizeof(SadRec));
-    }
-  SadArgs a{};
-  a.W = W; a.H = H; a.D = D; a.nn = nn; a.z = z; a.nch = nch;
-  a.bw = (64 + span_x + 63) & ~63;  // whole 64-pixel LDS-DMA pieces per band row
-  // a step's band spans at most RR + ceil(span_y) rows (sad_band_of: the
-  // truncated ends differ by < RR + span_y); one spare row for the float
-  // rounding of fractional shifts, none when every shift is integral
-  a.brows = RR + (int)std::ceil(span_y) + (aff ? 0 : 1);
-  const size_t lds = 16 * 2 * (size_t)a.brows * a.bw + (aff ? 0 : 4 * 2 * (size_t)DC * RR);
-  // band columns: SB_NBLK pieces of 64 at most (the systolic tile's reach)
-  if (a.bw > 64 * SB_NBLK) return 1;
-  if (lds > 160 * 1024 || (size_t)4 * TH * 64 * 8 > 16 * 2 * (size_t)a.brows * a.bw) return 1;
-  int rc = 0;
-  const int32_t* dev = plan_upload(ctx, table, &rc);
-  if (rc) return rc;
-  a.tiles_x = (W + SB_TW - 1) / SB_TW;
-  a.ntiles = a.tiles_x * ((H + TH - 1) / TH);
-  a.tiles_per_xcd = (a.ntiles + 7) / 8;
-  auto kern = k_sad_band<TH, PPW>;
-  if (aff) kern = a.bw == 64 ? k_sad_band<TH, PPW, true, 64> : k_sad_band<TH, PPW, true, 128>;
-  MVS_HIP(raise_lds(ctx, (const void*)kern, lds), "hipFuncSetAttribute(sad lds)");
-  hipLaunchKernelGGL(kern, dim3(8 * a.tiles_per_xcd), dim3(256), lds, ctx->stream, (const float4*)lab,
-                     ctx->d_levels, (const SadRec*)dev, a, disp);
-  MVS_LAUNCH_CHECK("k_sad_band");
-  return 0;
+// the k_sad_band instantiation of a band plan (TH = 8; BWT: 0 with the row table, else 64 or 128)
+using SadBandKernel = void (*)(const float4*, const float*, const SadRec*, SadArgs, float*);
+SadBandKernel sad_band_kernel(const plan::SadPlan& p) {
+  static constexpr SadBandKernel k[2][3] = {
+      {k_sad_band<8, 2>, k_sad_band<8, 2, true, 64>, k_sad_band<8, 2, true, 128>},
+      {k_sad_band<8, 1>, k_sad_band<8, 1, true, 64>, k_sad_band<8, 1, true, 128>}};
+  return k[p.PPW == 1][!p.AFF ? 0 : p.BWT == 64 ? 1 : 2];
 }
-
 }  // namespace
 
+// The per-pixel SAD sweep, one launch per reference view as plan_sad
+// (launch_plan.cpp) chooses: a band-staged form, or the gather kernel.
 int launch_sweep_pixel_sad(mvs_ctx* ctx, int V, int W, int H, const float* lab, const float* levels_host, int D,
                            const int* vs_host, const int* sn_host, int aw, float bl, int z0, int z1, float* disp) {
-  // MVS_SAD_KERNEL: "sys8x2", "sys8", "gather" (A/B and tests).  Without it:
-  // 16-level chunks, else 8-level chunks (taller bands: vertical neighbours),
-  // else the gather kernel.  A band variant named explicitly never falls back
-  // (MVS_E_UNSUPPORTED), so a test of it cannot pass on another.
-  const char* kv = getenv("MVS_SAD_KERNEL");
-  const std::string kind = kv ? kv : "auto";
-  const bool strict = kv != nullptr && kind != "gather";
+  const plan::Tuning t = plan::plan_tuning();
   const long P = (long)W * H;
   for (int z = z0; z < z1; z++) {
     float* out = disp + (long)(z - z0) * P;
-    int rc = 1;
-    if (kind == "auto") {
-      rc = launch_sad_band_t<8, 2>(ctx, V, W, H, lab, levels_host, D, vs_host, sn_host, aw, bl, z, out);
-      if (rc == 1) rc = launch_sad_band_t<8, 1>(ctx, V, W, H, lab, levels_host, D, vs_host, sn_host, aw, bl, z, out);
-    } else if (kind == "sys8")
-      rc = launch_sad_band_t<8, 1>(ctx, V, W, H, lab, levels_host, D, vs_host, sn_host, aw, bl, z, out);
-    else if (kind == "sys8x2")
-      rc = launch_sad_band_t<8, 2>(ctx, V, W, H, lab, levels_host, D, vs_host, sn_host, aw, bl, z, out);
-    if (rc < 0) return rc;
-    if (rc == 1 && strict) {
-      set_error("k_sad_band variant " + kind + " cannot stage this geometry (MVS_SAD_KERNEL set explicitly)");
+    const plan::SadPlan p = plan::plan_sad(t, V, W, H, D, levels_host, vs_host, sn_host, aw, bl, z);
+    if (!p.err.empty()) {
+      set_error(p.err);
       return MVS_E_UNSUPPORTED;
     }
-    if (rc == 1) {
+    const dim3 g(p.grid_x, p.grid_y);
+    if (p.band) {
+      int rc = 0;
+      const int32_t* dev = plan_upload(ctx, p.table, &rc);
+      if (rc) return rc;
+      const SadBandKernel kern = sad_band_kernel(p);
+      MVS_HIP(raise_lds(ctx, (const void*)kern, p.lds), "hipFuncSetAttribute(sad lds)");
+      hipLaunchKernelGGL(kern, g, dim3(256), p.lds, ctx->stream, (const float4*)lab, ctx->d_levels,
+                         (const SadRec*)dev, p.args, out);
+      MVS_LAUNCH_CHECK("k_sad_band");
+    } else {
       SweepArgs a{V, W, H, W, H, D, aw, z, bl};
-      hipLaunchKernelGGL(k_sweep_pixel_sad, dim3((W + PT - 1) / PT, (H + PT - 1) / PT), dim3(256), 0, ctx->stream,
-                         (const float4*)lab, ctx->d_levels, ctx->d_vs, ctx->d_sn, a, out);
+      hipLaunchKernelGGL(k_sweep_pixel_sad, g, dim3(256), 0, ctx->stream, (const float4*)lab, ctx->d_levels,
+                         ctx->d_vs, ctx->d_sn, a, out);
       MVS_LAUNCH_CHECK("k_sweep_pixel_sad");
     }
   }
