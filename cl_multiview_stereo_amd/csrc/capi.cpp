@@ -220,60 +220,12 @@ int mvs_slic_d(mvs_ctx* c, float* lab, int V, int W, int H, const mvs_slic_param
   if (p->no_iter < 0) return mvs::arg_fail("mvs_slic_d: no_iter < 0");
   if (p->edge_enable < 0 || p->edge_enable > 2) return mvs::arg_fail("mvs_slic_d: edge_enable must be 0, 1 or 2");
   if (p->search != 0 && p->search != 1) return mvs::arg_fail("mvs_slic_d: search must be 0 or 1");
-  // clSLIC ctor, clSLIC.cpp:15-18 (host float arithmetic)
-  float xy = 1.0f / (1.4242f * (float)S);
-  float col = 15.0f / (1.7321f * 128.0f);
-  xy = xy * xy;
-  col = col * col;
-  hipStream_t s = c->stream;
-  // one scratch for the update partials and the connectivity pass
-  // (the edge step's magnitude plane uses it before the first assignment)
-  size_t sb = std::max(mvs::update_scratch_bytes(V, W, H, S),
-                       p->enforce_connectivity ? sizeof(uint32_t) * (size_t)V * W * H : (size_t)0);
-  if (p->edge_enable) sb = std::max(sb, sizeof(float) * (size_t)V * W * H);
-  // the window-walk update (S % 16 != 0) reads 16-bit copies of the labels
-  // that each assignment writes beside them (labels < 65536); the scratch is
-  // free then (the edge plane is consumed before the first assignment, the
-  // connectivity pass runs after the last)
-  const bool l16 = S % 16 != 0 && p->no_iter > 0 && (long)mvs::map_dim(W, S) * mvs::map_dim(H, S) <= 65536;
-  if (l16) sb = std::max(sb, sizeof(uint16_t) * (size_t)V * W * H);
+  const mvs::plan::SlicPlan sp = mvs::plan::plan_slic(mvs::plan::plan_tuning(), V, W, H, S, p->no_iter, p->edge_enable,
+                                                      p->search, p->enforce_connectivity);
   int rc = 0;
-  void* scr = sb ? mvs::scratch(c, sb, &rc) : nullptr;
+  void* scr = sp.scratch_bytes ? mvs::scratch(c, sp.scratch_bytes, &rc) : nullptr;
   if (rc) return rc;
-  float* part = mvs::update_scratch_bytes(V, W, H, S) ? (float*)scr : nullptr;
-  RC(mvs::launch_init_centers(s, lab, V, W, H, S, spixl));
-  RC(mvs::launch_edge_step(s, lab, V, W, H, S, p->edge_enable, spixl, (float*)scr));
-  if (part && S % 16 == 0) {
-    // assign -> (update -> assign) x no_iter with each update's tile partials
-    // produced by the assign pass before it (one Lab read per iteration)
-    // (an assignment an update follows stores no labels: the update reads its partials only)
-    RC(mvs::launch_assign_tiles(s, lab, spixl, V, W, H, S, xy, col, p->color_weight, p->search,
-                                p->no_iter > 0 ? nullptr : labels, p->no_iter > 0 ? part : nullptr));
-    for (int i = 0; i < p->no_iter; i++) {
-      RC(mvs::launch_update_finalize(s, part, V, W, H, S, spixl));
-      const bool more = i + 1 < p->no_iter;
-      RC(mvs::launch_assign_tiles(s, lab, spixl, V, W, H, S, xy, col, p->color_weight, p->search,
-                                  more ? nullptr : labels, more ? part : nullptr));
-    }
-  } else {
-    uint16_t* lb16 = l16 ? (uint16_t*)scr : nullptr;
-    // with the 16-bit copies, an assignment an update follows writes only them
-    // (the updates read nothing else); the last one writes the 32-bit labels
-    RC(mvs::launch_assign(s, lab, spixl, V, W, H, S, xy, col, p->color_weight, p->search, lb16 ? nullptr : labels,
-                          lb16));
-    for (int i = 0; i < p->no_iter; i++) {
-      RC(mvs::launch_update(s, lab, labels, V, W, H, S, spixl, part, lb16));
-      const bool more = i + 1 < p->no_iter;
-      RC(mvs::launch_assign(s, lab, spixl, V, W, H, S, xy, col, p->color_weight, p->search,
-                            more && lb16 ? nullptr : labels, more ? lb16 : nullptr));
-    }
-  }
-  if (p->enforce_connectivity) {
-    uint32_t* tmp = (uint32_t*)scr;
-    RC(mvs::launch_suppress(s, labels, tmp, V, W, H));
-    RC(mvs::launch_suppress(s, tmp, labels, V, W, H));
-  }
-  return 0;
+  return mvs::launch_slic(c, sp, p->color_weight, lab, spixl, labels, scr);
 }
 
 int mvs_boundary_d(mvs_ctx* c, int V, int W, int H, int S, const float* spixl, const uint32_t* labels,

@@ -1,6 +1,7 @@
 // The launch planners of launch_plan.h.  Host code only; built with
 // -ffp-contract=off: the HZ and SAD tests compare the kernels' float products
-// d * (float)dx and (bl * d) * (float)dy.
+// d * (float)dx and (bl * d) * (float)dy, and the SLIC normalisers are the
+// reference's host float arithmetic.
 #include "launch_plan.h"
 
 #include <algorithm>
@@ -50,7 +51,87 @@ Tuning plan_tuning() {
   t.filter_ns = num("MVS_FILTER_NS", 2);
   t.filter_bound = num("MVS_FILTER_BOUND", 1) != 0;
   t.filter_ref_order = is("MVS_FILTER_ORDER", "ref");
+  t.slic_tiles9 = num("MVS_SLIC_TILES9", 0) == 1;
+  t.slic_update_walk = num("MVS_SLIC_UPDATE", 1) != 0;
   return t;
+}
+
+SlicPlan plan_slic(const Tuning& t, int V, int W, int H, int S, int no_iter, int edge_enable, int search,
+                   int enforce_connectivity) {
+  SlicPlan p;
+  p.V = V, p.W = W, p.H = H, p.S = S;
+  const int mw = p.mw = map_dim(W, S), mh = p.mh = map_dim(H, S);
+  // clSLIC ctor, clSLIC.cpp:15-18 (host float arithmetic)
+  float xy = 1.0f / (1.4242f * (float)S);
+  float col = 15.0f / (1.7321f * 128.0f);
+  p.xy = xy * xy;
+  p.col = col * col;
+  const bool tiles = S % kLocal == 0;
+  const int cpl = p.cpl = S * 3 / kLocal;
+  // (the two agree where both apply; each path keeps the reference's formula it was written with)
+  const int G = p.G = tiles ? cpl * cpl : (int)__builtin_ceilf((float)(S * S * 9) / (float)(kLocal * kLocal));
+  const int ntx = p.ntx = (W + 15) / 16, nty = p.nty = (H + 15) / 16;
+  const size_t P = (size_t)V * W * H;
+  const bool l16 = !tiles && no_iter > 0 && (long)mw * mh <= 65536;
+  size_t sb = tiles ? sizeof(float) * 6 * (size_t)G * mw * mh * V : 0;
+  if (enforce_connectivity || edge_enable) sb = std::max(sb, sizeof(uint32_t) * P);
+  if (l16) sb = std::max(sb, sizeof(uint16_t) * P);
+  p.scratch_bytes = sb;
+
+  p.steps.reserve(6 + 2 * (size_t)no_iter);
+  const auto step = [&p](SlicKernel k, unsigned gx, unsigned gy, unsigned gz, unsigned block) -> SlicStep& {
+    p.steps.push_back(SlicStep{k, 0, 0, 0, 0, 0, {gx, gy, gz}, block, false, false, false, false});
+    return p.steps.back();
+  };
+  const unsigned cx = (mw + 63) / 64, px = (W + 255) / 256;
+  step(kSlicInitCenters, cx, mh, V, 64);
+  if (edge_enable == 1 || edge_enable == 2) {  // clSLIC::apply_edge_values (clSLIC.cpp:186-233)
+    step(kSlicEdge, px, H, V, 256);
+    // 1, the reference's path: the magnitude into the Lab image;
+    // apply_edge_alternative then reads the never-written edge_img (pinned as
+    // zeros): no centre moves
+    if (edge_enable == 1)
+      step(kSlicEdgeStore, (unsigned)std::min<long>(((long)P + 255) / 256, 8192), 1, 1, 256);
+    else
+      step(kSlicApplyEdge, cx, mh, V, 64);
+  }
+  // k_assign_tiles4: the 2x2 loop at S = 32 or 64, 32-bit byte offsets into a view and into part
+  const bool tiles4 = !search && (S == 32 || S == 64) && (long)W * H * 16 < (1L << 31) &&
+                      (long)mw * mh * G * 24 < (1L << 31) && !t.slic_tiles9;
+  // more: an update follows this assignment
+  const auto assign = [&](bool more) {
+    if (tiles) {
+      SlicStep& s = tiles4 ? step(kSlicAssignTiles4, (ntx + 3) / 4, nty, V, 256)
+                           : step(kSlicAssignTiles9, (ntx * nty + 3) / 4, V, 1, 256);
+      if (tiles4)
+        s.S16 = S / 16;
+      else
+        s.S3 = search;
+      s.labels = !more, s.part = more;
+    } else {
+      SlicStep& s = step(kSlicAssign, (W + kAssignTW - 1) / kAssignTW, (H + kAssignTH - 1) / kAssignTH, V, 256);
+      s.S3 = search;
+      s.labels = !(more && l16), s.lb16 = more && l16;
+    }
+  };
+  // k_update_walk's 32-bit byte offsets span a view's Lab: W H 16 < 2^31
+  const bool walk = (long)W * H * 16 < (1L << 31) && t.slic_update_walk;
+  assign(no_iter > 0);
+  for (int i = 0; i < no_iter; i++) {
+    if (tiles) {
+      step(kSlicUpdateFinalize, (mw * mh + 31) / 32, V, 1, 256).CPL = cpl == 6 ? 6 : 0;
+    } else {
+      SlicStep& s = step(walk ? kSlicUpdateWalk : kSlicUpdate, (mw * mh + 3) / 4, V, 1, 256);
+      s.UT = G > 4 ? 4 : 1;
+      s.LT = l16 ? 16 : 32;
+    }
+    assign(i + 1 < no_iter);
+  }
+  if (enforce_connectivity) {
+    step(kSlicSuppress, px, H, V, 256).to_scratch = true;
+    step(kSlicSuppress, px, H, V, 256);
+  }
+  return p;
 }
 
 SpixlSweepPlan plan_sweep_spixl(const Tuning& t, int V, int W, int H, int S, int D, const float* levels,

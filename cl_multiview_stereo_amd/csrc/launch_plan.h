@@ -1,11 +1,13 @@
-// The launch planners of the superpixel sweep, the per-pixel SAD sweep and the
-// view-consistency filter: every host-side decision of launch_sweep_spixl,
-// launch_sweep_pixel_sad and launch_remove_incons (kernel form, grids, the
-// re-layout slot table, the SAD step records, LDS bytes) as plain C++ with no
-// HIP header and no mvs_ctx, so it builds with g++ and runs without a GPU
-// (tests/host/launch_plan_check.cpp prints its decisions).  sweep.hip and
-// refine.hip map a plan to a kernel instantiation and launch it.  The structs
-// and constants below that a kernel reads too are defined here once.
+// The launch planners of the SLIC stage, the superpixel sweep, the per-pixel
+// SAD sweep and the view-consistency filter: every host-side decision of
+// launch_slic, launch_sweep_spixl, launch_sweep_pixel_sad and
+// launch_remove_incons (the SLIC launch sequence and its shared scratch, kernel
+// form, grids, the re-layout slot table, the SAD step records, LDS bytes) as
+// plain C++ with no HIP header and no mvs_ctx, so it builds with g++ and runs
+// without a GPU (tests/host/launch_plan_check.cpp prints its decisions).
+// slic.hip, sweep.hip and refine.hip map a plan to a kernel instantiation and
+// launch it.  The structs and constants below that a kernel reads too are
+// defined here once.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -18,6 +20,10 @@ inline int map_dim(int n, int S) {
   // (int)ceil((float)n / (float)S), pipeline.cpp:18-19
   return (int)__builtin_ceilf((float)n / (float)S);
 }
+
+// ---- shared with the SLIC kernels (slic.hip) --------------------------------
+constexpr int kLocal = 16;  // LOCAL_SIZE_UPDATE, header.h:37-38: the update's tile edge
+constexpr int kAssignTW = 64, kAssignTH = 16;  // k_assign's pixel tile (AS_TW, AS_TH)
 
 // ---- shared with k_sweep_spixl_ring (sweep.hip) ----------------------------
 constexpr int kSwU = 336;  // C5 (S = 40, |dx| <= 4): 78 + 2 + 252 = 332
@@ -46,9 +52,11 @@ constexpr int kFilterRG = 4;  // reference views per workgroup of the q kernel
 
 namespace plan {
 
-// Every knob of the three launchers.  plan_tuning() is the one place that
+// Every knob of the four launchers.  plan_tuning() is the one place that
 // reads them, all of them per call.
 struct Tuning {
+  bool slic_tiles9 = false;     // MVS_SLIC_TILES9=1: the 9-cell k_assign_tiles where k_assign_tiles4 would run (A/B)
+  bool slic_update_walk = true;  // MVS_SLIC_UPDATE=0: k_update where k_update_walk would run (A/B)
   int sweep_wps = 0;        // MVS_SWEEP_WPS=1|2|4: another wave count per superpixel (0: automatic; ignored at D <= 32)
   int sweep_transpose = 2;  // MVS_SWEEP_TRANSPOSE: 0 row-major gathers only, 1 vertical neighbours re-laid, 2 diagonal ones too
   bool sweep_hz = true;     // MVS_SWEEP_HZ=0: the general form where HZ would run
@@ -68,6 +76,66 @@ struct Tuning {
   bool filter_ref_order = false;  // MVS_FILTER_ORDER=ref: the q kernel's grid as (x tiles, rows, reference groups)
 };
 Tuning plan_tuning();
+
+// ---- launch_slic --------------------------------------------------------------
+enum SlicKernel {
+  kSlicInitCenters, kSlicEdge, kSlicEdgeStore, kSlicApplyEdge,
+  kSlicAssign,          // k_assign<S3>
+  kSlicAssignTiles9,    // k_assign_tiles<S3>
+  kSlicAssignTiles4,    // k_assign_tiles4<S16>
+  kSlicUpdateFinalize,  // k_update_finalize<CPL>
+  kSlicUpdateWalk,      // k_update_walk<UT, uintLT_t>
+  kSlicUpdate,          // k_update<UT, uintLT_t>
+  kSlicSuppress
+};
+// One launch.  A kernel's pointer arguments are the caller's lab, spixl and
+// labels or the context scratch; the flags say which where there is a choice.
+struct SlicStep {
+  SlicKernel kernel;
+  // the template coordinates (0 where the kernel has none): S3 the 3x3
+  // candidate loop (search); S16 = S / 16 (2 | 4); CPL 6 | 0; UT tiles per
+  // chunk 4 | 1; LT the width of the labels an update reads, 16 | 32
+  int S3, S16, CPL, UT, LT;
+  unsigned grid[3], block;
+  bool labels;      // an assignment stores the 32-bit labels (else it gets null: an update follows that does not read them)
+  bool lb16;        // k_assign stores 16-bit label copies into the scratch (else null); LT = 16 reads them there
+  bool part;        // a tile assignment stores the next update's tile partials into the scratch (else null)
+  bool to_scratch;  // k_suppress: labels -> scratch (else scratch -> labels)
+};
+// The whole stage: init centres, the edge step (edge_enable 1: k_edge,
+// k_edge_store; 2: k_edge, k_apply_edge), then assign -> (update -> assign) x
+// no_iter, then two k_suppress passes (enforce_connectivity).
+//  * S % 16 == 0, the tile path: every assignment an update follows produces
+//    that update's tile partials itself and stores no labels (one Lab read per
+//    iteration); the update is k_update_finalize's sum of them.
+//  * else: k_assign, and k_update_walk over the labels (k_update: when the
+//    walk's 32-bit byte offsets do not cover a view, W H 16 >= 2^31, or by
+//    MVS_SLIC_UPDATE=0).  With mw mh <= 65536 and no_iter > 0 the updates read
+//    16-bit copies of the labels: an assignment an update follows writes only
+//    them, the last one only the 32-bit labels.
+// One scratch of scratch_bytes (0: none) serves four users whose lifetimes do
+// not overlap, so it is the largest of them:
+//  1. the edge magnitude plane (V W H floats): k_edge writes it, k_edge_store /
+//     k_apply_edge read it, all before the first assignment;
+//  2. the tile partials (S % 16 == 0; 6 G floats per superpixel): written by
+//     an assignment, read by the k_update_finalize after it;
+//  3. the 16-bit labels (never with 2: S % 16 != 0): written by an
+//     assignment, read by the update after it;
+//  4. the connectivity pass's second label buffer (V W H uint32): after the
+//     last assignment, which writes neither 2 nor 3.
+struct SlicPlan {
+  int V = 0, W = 0, H = 0, S = 0;
+  int mw = 0, mh = 0;
+  float xy = 0, col = 0;  // clSLIC's squared distance normalisers
+  // num_grid_per_center, cluster_per_line (clSLIC.cpp:20-21, 313) and the
+  // image's 16 x 16 tile grid
+  int G = 0, cpl = 0, ntx = 0, nty = 0;
+  size_t scratch_bytes = 0;
+  std::vector<SlicStep> steps;  // in launch order
+};
+// The caller has checked the arguments (mvs_slic_d: S in [6, 96], no_iter >= 0, ...).
+SlicPlan plan_slic(const Tuning& t, int V, int W, int H, int S, int no_iter, int edge_enable, int search,
+                   int enforce_connectivity);
 
 // ---- launch_sweep_spixl -----------------------------------------------------
 // the form of a launch, as mvs_sweep_last_variant_n reports it

@@ -13,7 +13,7 @@
 
 #include "../../include/mvs.h"
 #include "../../include/mvs_detmath.h"
-#include "launch_plan.h"  // map_dim, and what the sweep / SAD / filter kernels share with their planners
+#include "launch_plan.h"  // map_dim, and what the SLIC / sweep / SAD / filter kernels share with their planners
 
 struct mvs_ctx {
   int device = 0;
@@ -85,8 +85,6 @@ int arg_fail(const char* what);
 void* scratch(mvs_ctx* ctx, size_t bytes, int* rc);
 const int32_t* plan_upload(mvs_ctx* ctx, const std::vector<int32_t>& table, int* rc);
 
-constexpr int kLocal = 16;  // LOCAL_SIZE_UPDATE, header.h:37-38
-
 #define MVS_LAUNCH_CHECK(what)                          \
   do {                                                  \
     hipError_t _e = hipGetLastError();                  \
@@ -103,23 +101,15 @@ constexpr int kLocal = 16;  // LOCAL_SIZE_UPDATE, header.h:37-38
 int launch_cvt(hipStream_t s, const uint8_t* rgbx, long npix, float* lab, uint8_t* l8);
 int launch_init_centers(hipStream_t s, const float* lab, int V, int W, int H, int S, float* spixl);
 int launch_grid_labels(hipStream_t s, int V, int W, int H, int S, uint32_t* labels);
-int launch_edge_step(hipStream_t s, float* lab, int V, int W, int H, int S, int edge_enable, float* spixl,
-                     float* edge);
-int launch_assign(hipStream_t s, const float* lab, const float* spixl, int V, int W, int H, int S, float xy_n,
-                  float col_n, float weight, int search, uint32_t* labels, uint16_t* lb16 = nullptr);
-size_t update_scratch_bytes(int V, int W, int H, int S);
-int launch_assign_tiles(hipStream_t s, const float* lab, const float* spixl, int V, int W, int H, int S, float xy_n,
-                        float col_n, float weight, int search, uint32_t* labels, float* part);
-int launch_update_finalize(hipStream_t s, const float* part, int V, int W, int H, int S, float* spixl);
-int launch_update(hipStream_t s, const float* lab, const uint32_t* labels, int V, int W, int H, int S,
-                  float* spixl, float* part, const uint16_t* lb16 = nullptr);
-int launch_suppress(hipStream_t s, const uint32_t* in, uint32_t* out, int V, int W, int H);
 
 int launch_boundary(hipStream_t s, int V, int W, int H, int S, const float* spixl, const uint32_t* labels,
                     uint8_t* rep);
-// launch_sweep_spixl, launch_sweep_pixel_sad and launch_remove_incons decide
-// nothing themselves: launch_plan.cpp plans (kernel form, grids, tables, LDS),
-// they upload the tables and map the plan to a kernel instantiation
+// launch_slic, launch_sweep_spixl, launch_sweep_pixel_sad and
+// launch_remove_incons decide nothing themselves: launch_plan.cpp plans (the
+// SLIC launch sequence, kernel form, grids, tables, LDS), they upload the
+// tables and map the plan to a kernel instantiation
+int launch_slic(mvs_ctx* ctx, const plan::SlicPlan& p, float weight, float* lab, float* spixl, uint32_t* labels,
+                void* scratch);
 int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* lab, float* spixl,
                        const uint8_t* rep, const float* levels, int D, const int* vs, const int* sn, int aw,
                        float bl, int z0, int z1);

@@ -676,77 +676,21 @@ __global__ __launch_bounds__(256) void k_update_walk(const float4* __restrict__ 
   }
 }
 
-// ---- the same update when S is a multiple of 16 --------------------------
-// Every superpixel window then starts on the global 16x16 tile grid, so each
-// image tile is tile t = nby*cpl + nbx of exactly the 3x3 superpixels whose
-// windows cover it.  One wave per image tile reads its 256 pixels ONCE (the
-// per-superpixel kernel above reads each pixel 9 times) and reduces, for each
-// of those superpixels, its members with the reference's LDS tree order
-// (wave_tree); non-members and other superpixels contribute exact zeros.
-// k_update_finalize then sums each superpixel's G partials in tile order --
-// bit-identical to k_update.
-__global__ __launch_bounds__(256) void k_update_tiles(const float4* __restrict__ lab,
-                                                      const uint32_t* __restrict__ labels, int W, int H, int S,
-                                                      int mw, int mh, int G, int cpl, int ntx, int nty,
-                                                      float* __restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tile = blockIdx.x * 4 + wave, z = blockIdx.y;
-  if (tile >= ntx * nty) return;  // no barriers below
-  const int TX = tile % ntx, TY = tile / ntx, s16 = S / 16;
-  const long P = (long)W * H;
-  const float4* L = lab + (long)z * P;
-  const uint32_t* I = labels + (long)z * P;
-  const int lx = lane & 15, ly0 = lane >> 4;  // local index k = lane + 64*m, as the reference tile
-  uint32_t lbl[4];
-  float4 c[4];
-  float fx[4], fy[4];
-#pragma unroll
-  for (int m = 0; m < 4; m++) {
-    const int px = TX * 16 + lx, py = TY * 16 + ly0 + 4 * m;
-    const bool in = px < W && py < H;
-    lbl[m] = in ? I[(long)py * W + px] : 0xffffffffu;
-    c[m] = in ? L[(long)py * W + px] : make_float4(0.f, 0.f, 0.f, 0.f);
-    fx[m] = (float)px;
-    fy[m] = (float)py;
-  }
-  float* out = part + (long)z * mw * mh * G * 6;
-  for (int gy = TY / s16 - 1; gy <= TY / s16 + 1; gy++) {
-    if (gy < 0 || gy >= mh) continue;
-    for (int gx = TX / s16 - 1; gx <= TX / s16 + 1; gx++) {
-      if (gx < 0 || gx >= mw) continue;
-      const uint32_t sp = (uint32_t)(gy * mw + gx);
-      const int t = (TY - (gy - 1) * s16) * cpl + (TX - (gx - 1) * s16);
-      bool mem[4], any = false;
-#pragma unroll
-      for (int m = 0; m < 4; m++) {
-        mem[m] = lbl[m] == sp;
-        any |= mem[m];
-      }
-      float r[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (__any(any)) {
-        r[0] = wave_tree(mem[0] ? fx[0] : 0.f, mem[1] ? fx[1] : 0.f, mem[2] ? fx[2] : 0.f, mem[3] ? fx[3] : 0.f);
-        r[1] = wave_tree(mem[0] ? fy[0] : 0.f, mem[1] ? fy[1] : 0.f, mem[2] ? fy[2] : 0.f, mem[3] ? fy[3] : 0.f);
-        r[2] = wave_tree(mem[0] ? c[0].x : 0.f, mem[1] ? c[1].x : 0.f, mem[2] ? c[2].x : 0.f, mem[3] ? c[3].x : 0.f);
-        r[3] = wave_tree(mem[0] ? c[0].y : 0.f, mem[1] ? c[1].y : 0.f, mem[2] ? c[2].y : 0.f, mem[3] ? c[3].y : 0.f);
-        r[4] = wave_tree(mem[0] ? c[0].z : 0.f, mem[1] ? c[1].z : 0.f, mem[2] ? c[2].z : 0.f, mem[3] ? c[3].z : 0.f);
-        r[5] = wave_tree(mem[0] ? 1.f : 0.f, mem[1] ? 1.f : 0.f, mem[2] ? 1.f : 0.f, mem[3] ? 1.f : 0.f);
-      }
-      if (lane == 0) {  // the tree's result lives in lane 0
-#pragma unroll
-        for (int ch = 0; ch < 6; ch++) out[((long)sp * G + t) * 6 + ch] = r[ch];
-      }
-    }
-  }
-}
-
 // ---- assignment fused with the next update's tile partials ----------------
-// (S % 16 == 0) One wave per 16x16 image tile: the tile lies inside one
-// superpixel cell, so every candidate centre of its pixels is one of the 3x3
-// cells around it (staged in LDS per wave).  The wave assigns its 256 pixels
-// exactly as k_assign (same arithmetic, same tie rule), stores the labels
-// and, when part != nullptr, reduces the tile for each covering superpixel
-// exactly as k_update_tiles would from those labels -- one read of Lab per
-// SLIC iteration instead of two.
+// (S % 16 == 0) Every superpixel window then starts on the global 16x16 tile
+// grid, so each image tile is tile t = nby*cpl + nbx of exactly the 3x3
+// superpixels whose windows cover it.  One wave per image tile: the tile lies
+// inside one superpixel cell, so every candidate centre of its pixels is one
+// of the 3x3 cells around it (staged in LDS per wave).  The wave assigns its
+// 256 pixels exactly as k_assign (same arithmetic, same tie rule), stores the
+// labels and, when part != nullptr, reduces the tile for each of those
+// superpixels: its members with the reference's LDS tree order (wave_tree),
+// non-members and other superpixels contributing exact zeros -- the tile
+// partial k_update forms for window tile t, from a pixel read ONCE (the
+// per-superpixel kernels above read each pixel 9 times) and from the Lab
+// values the assignment already holds: one read of Lab per SLIC iteration
+// instead of two.  k_update_finalize then sums each superpixel's G partials
+// in tile order -- bit-identical to k_update.
 template <bool S3>
 __global__ __launch_bounds__(256) void k_assign_tiles(const float4* __restrict__ lab,
                                                       const float* __restrict__ spixl, int W, int H, int S, int mw,
@@ -879,8 +823,8 @@ typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 //  * the update reduces only the four candidate cells, their trees
 //    interleaved (16 independent chains per wave instead of one cell's four at
 //    a time behind a branch); the other in-image cells of the 3x3 around the
-//    tile, which no pixel of the tile can join, get the exact zeros k_update_tiles
-//    would write for them.
+//    tile, which no pixel of the tile can join, get the exact zeros the
+//    9-cell k_assign_tiles writes for them.
 // (The 9-cell loop measured 71-83 us per C2 launch: 40 % of its wave cycles
 // stalled on instruction dependencies, 632 SALU instructions per wave.)
 // S16 = S / 16 (2: S = 32, 4: S = 64): divisions by constants.  Grid
@@ -1210,28 +1154,6 @@ int launch_init_centers(hipStream_t s, const float* lab, int V, int W, int H, in
   return 0;
 }
 
-// clSLIC::apply_edge_values (clSLIC.cpp:186-233); edge = V*W*H floats scratch
-int launch_edge_step(hipStream_t s, float* lab, int V, int W, int H, int S, int edge_enable, float* spixl,
-                     float* edge) {
-  if (edge_enable != 1 && edge_enable != 2) return 0;
-  hipLaunchKernelGGL(k_edge, dim3((W + 255) / 256, H, V), dim3(256), 0, s, (const float4*)lab, W, H, edge);
-  MVS_LAUNCH_CHECK("k_edge");
-  if (edge_enable == 1) {
-    // the reference's path: magnitude into the Lab image; apply_edge_alternative
-    // then reads the never-written edge_img (pinned as zeros): no centre moves
-    const long n = (long)V * W * H;
-    hipLaunchKernelGGL(k_edge_store, dim3((unsigned)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, s, edge, n,
-                       (float4*)lab);
-    MVS_LAUNCH_CHECK("k_edge_store");
-    return 0;
-  }
-  const int mw = map_dim(W, S), mh = map_dim(H, S);
-  hipLaunchKernelGGL(k_apply_edge, dim3((mw + 63) / 64, mh, V), dim3(64), 0, s, (const float4*)lab, edge, W, H, mw,
-                     mh, spixl);
-  MVS_LAUNCH_CHECK("k_apply_edge");
-  return 0;
-}
-
 int launch_grid_labels(hipStream_t s, int V, int W, int H, int S, uint32_t* labels) {
   int mw = map_dim(W, S);
   hipLaunchKernelGGL(k_grid_labels, dim3((W + 255) / 256, H, V), dim3(256), 0, s, W, H, S, mw, labels);
@@ -1239,102 +1161,82 @@ int launch_grid_labels(hipStream_t s, int V, int W, int H, int S, uint32_t* labe
   return 0;
 }
 
-int launch_assign(hipStream_t s, const float* lab, const float* spixl, int V, int W, int H, int S, float xy_n,
-                  float col_n, float weight, int search, uint32_t* labels, uint16_t* lb16) {
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  if (!labels && !(lb16 && (long)mw * mh <= 65536)) return arg_fail("SLIC assign: no label output");
-  if ((AS_TW / S + 4) * (AS_TH / S + 4) > AS_MAXC) return arg_fail("SLIC assign: spixl_size too small");
-  hipLaunchKernelGGL(search ? k_assign<true> : k_assign<false>, dim3((W + AS_TW - 1) / AS_TW, (H + AS_TH - 1) / AS_TH, V), dim3(256), 0, s,
-                     (const float4*)lab, spixl, W, H, S, mw, mh, xy_n, col_n, weight, labels,
-                     (long)mw * mh <= 65536 ? lb16 : nullptr);
-  MVS_LAUNCH_CHECK("k_assign");
-  return 0;
-}
+// k_assign's tile as the planner sizes its grid; its centre table holds the
+// (AS_TW / S + 4) (AS_TH / S + 4) <= (64 / 6 + 4) (16 / 6 + 4) = 84 candidate
+// centres of a tile for every S >= 6 (mvs_slic_d's lower bound)
+static_assert(AS_TW == kAssignTW && AS_TH == kAssignTH, "plan_slic sizes k_assign's grid");
+static_assert((AS_TW / 6 + 4) * (AS_TH / 6 + 4) <= AS_MAXC, "k_assign's centre table at S >= 6");
 
-int launch_assign_tiles(hipStream_t s, const float* lab, const float* spixl, int V, int W, int H, int S, float xy_n,
-                        float col_n, float weight, int search, uint32_t* labels, float* part) {
-  if (S % 16 != 0) return arg_fail("SLIC fused assign needs spixl_size % 16 == 0");
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  int G = (3 * S / kLocal) * (3 * S / kLocal), cpl = S * 3 / kLocal;
-  int ntx = (W + 15) / 16, nty = (H + 15) / 16;
-  // MVS_SLIC_TILES9=1 (read per call): the 9-cell kernel for S % 32 == 0 too (A/B)
-  const char* t9 = getenv("MVS_SLIC_TILES9");
-  if (!search && (S == 32 || S == 64) && (long)W * H * 16 < (1L << 31) && (long)mw * mh * G * 24 < (1L << 31) &&
-      !(t9 && atoi(t9) == 1))
-    hipLaunchKernelGGL(S == 32 ? k_assign_tiles4<2> : k_assign_tiles4<4>, dim3((ntx + 3) / 4, nty, V), dim3(256), 0,
-                       s, (const float4*)lab, spixl, W, H, mw, mh, xy_n, col_n, weight, G, cpl, ntx, labels, part);
-  else
-    hipLaunchKernelGGL(search ? k_assign_tiles<true> : k_assign_tiles<false>, dim3((ntx * nty + 3) / 4, V), dim3(256), 0, s, (const float4*)lab, spixl, W,
-                       H, S, mw, mh, xy_n, col_n, weight, G, cpl, ntx, nty, labels, part);
-  MVS_LAUNCH_CHECK("k_assign_tiles");
-  return 0;
-}
-
-int launch_update_finalize(hipStream_t s, const float* part, int V, int W, int H, int S, float* spixl) {
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  int G = (3 * S / kLocal) * (3 * S / kLocal), cpl = S * 3 / kLocal;
-  int ntx = (W + 15) / 16, nty = (H + 15) / 16;
-  hipLaunchKernelGGL(cpl == 6 ? k_update_finalize<6> : k_update_finalize<0>, dim3((mw * mh + 31) / 32, V), dim3(256),
-                     0, s, part, mw, mh, S, G, cpl, ntx, nty, spixl);
-  MVS_LAUNCH_CHECK("k_update_finalize");
-  return 0;
-}
-
-size_t update_scratch_bytes(int V, int W, int H, int S) {
-  if (S % 16 != 0) return 0;
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  int G = (3 * S / kLocal) * (3 * S / kLocal);
-  return sizeof(float) * 6 * (size_t)G * mw * mh * V;
-}
-
-int launch_update(hipStream_t s, const float* lab, const uint32_t* labels, int V, int W, int H, int S,
-                  float* spixl, float* part, const uint16_t* lb16) {
-  int mw = map_dim(W, S), mh = map_dim(H, S);
-  int G = (int)__builtin_ceilf((float)(S * S * 9) / (float)(kLocal * kLocal));
-  int cpl = S * 3 / kLocal;
-  if (cpl <= 0) return arg_fail("SLIC update needs spixl_size >= 6 (cluster_per_line = 3S/16 > 0)");
-  if (part && S % 16 == 0) {  // tile-grid path (each pixel read once)
-    int ntx = (W + 15) / 16, nty = (H + 15) / 16;
-    hipLaunchKernelGGL(k_update_tiles, dim3((ntx * nty + 3) / 4, V), dim3(256), 0, s, (const float4*)lab, labels,
-                       W, H, S, mw, mh, G, cpl, ntx, nty, part);
-    MVS_LAUNCH_CHECK("k_update_tiles");
-    hipLaunchKernelGGL(cpl == 6 ? k_update_finalize<6> : k_update_finalize<0>, dim3((mw * mh + 31) / 32, V),
-                       dim3(256), 0, s, part, mw, mh, S, G, cpl, ntx, nty, spixl);
-    MVS_LAUNCH_CHECK("k_update_finalize");
-    return 0;
-  }
-  // k_update_walk (32-bit buffer offsets: P * 16 < 2^31); MVS_SLIC_UPDATE=0
-  // (read per call): k_update (A/B)
-  const char* ue = getenv("MVS_SLIC_UPDATE");
-  const bool walk = (long)W * H * 16 < (1L << 31) && !(ue && atoi(ue) == 0);
-  if (walk) {
-    const bool l16 = lb16 && (long)mw * mh <= 65536;
-    const dim3 g((mw * mh + 3) / 4, V);
-    if (l16) {
-      auto kw = G > 4 ? k_update_walk<4, uint16_t> : k_update_walk<1, uint16_t>;
-      hipLaunchKernelGGL(kw, g, dim3(256), 0, s, (const float4*)lab, lb16, W, H, S, mw, mh, G, cpl, spixl);
-    } else {
-      auto kw = G > 4 ? k_update_walk<4, uint32_t> : k_update_walk<1, uint32_t>;
-      hipLaunchKernelGGL(kw, g, dim3(256), 0, s, (const float4*)lab, labels, W, H, S, mw, mh, G, cpl, spixl);
+// The SLIC stage as plan_slic (launch_plan.cpp) laid it out: nothing is
+// decided here, a step is mapped to its kernel instantiation and launched.
+// scratch: p.scratch_bytes bytes (null when 0).
+int launch_slic(mvs_ctx* ctx, const plan::SlicPlan& p, float weight, float* lab, float* spixl, uint32_t* labels,
+                void* scratch) {
+  static const char* const names[] = {"k_init_centers", "k_edge",         "k_edge_store",      "k_apply_edge",
+                                      "k_assign",       "k_assign_tiles", "k_assign_tiles",    "k_update_finalize",
+                                      "k_update_walk",  "k_update",       "k_suppress"};
+  hipStream_t s = ctx->stream;
+  const float4* L = (const float4*)lab;
+  const int W = p.W, H = p.H, S = p.S, mw = p.mw, mh = p.mh, G = p.G, cpl = p.cpl;
+  for (const plan::SlicStep& st : p.steps) {
+    const dim3 g(st.grid[0], st.grid[1], st.grid[2]), b(st.block);
+    uint32_t* lo = st.labels ? labels : nullptr;
+    uint16_t* l16 = st.lb16 ? (uint16_t*)scratch : nullptr;
+    float* part = st.part ? (float*)scratch : nullptr;
+    switch (st.kernel) {
+      case plan::kSlicInitCenters:
+        hipLaunchKernelGGL(k_init_centers, g, b, 0, s, L, W, H, S, mw, mh, spixl);
+        break;
+      case plan::kSlicEdge:
+        hipLaunchKernelGGL(k_edge, g, b, 0, s, L, W, H, (float*)scratch);
+        break;
+      case plan::kSlicEdgeStore:
+        hipLaunchKernelGGL(k_edge_store, g, b, 0, s, (const float*)scratch, (long)p.V * W * H, (float4*)lab);
+        break;
+      case plan::kSlicApplyEdge:
+        hipLaunchKernelGGL(k_apply_edge, g, b, 0, s, L, (const float*)scratch, W, H, mw, mh, spixl);
+        break;
+      case plan::kSlicAssign:
+        hipLaunchKernelGGL(st.S3 ? k_assign<true> : k_assign<false>, g, b, 0, s, L, spixl, W, H, S, mw, mh, p.xy, p.col,
+                           weight, lo, l16);
+        break;
+      case plan::kSlicAssignTiles4:
+        hipLaunchKernelGGL(st.S16 == 2 ? k_assign_tiles4<2> : k_assign_tiles4<4>, g, b, 0, s, L, spixl, W, H, mw, mh,
+                           p.xy, p.col, weight, G, cpl, p.ntx, lo, part);
+        break;
+      case plan::kSlicAssignTiles9:
+        hipLaunchKernelGGL(st.S3 ? k_assign_tiles<true> : k_assign_tiles<false>, g, b, 0, s, L, spixl, W, H, S, mw,
+                           mh, p.xy, p.col, weight, G, cpl, p.ntx, p.nty, lo, part);
+        break;
+      case plan::kSlicUpdateFinalize:
+        hipLaunchKernelGGL(st.CPL == 6 ? k_update_finalize<6> : k_update_finalize<0>, g, b, 0, s,
+                           (const float*)scratch, mw, mh, S, G, cpl, p.ntx, p.nty, spixl);
+        break;
+      case plan::kSlicUpdateWalk:
+        if (st.LT == 16)
+          hipLaunchKernelGGL((st.UT == 4 ? k_update_walk<4, uint16_t> : k_update_walk<1, uint16_t>), g, b, 0, s, L,
+                             (const uint16_t*)scratch, W, H, S, mw, mh, G, cpl, spixl);
+        else
+          hipLaunchKernelGGL((st.UT == 4 ? k_update_walk<4, uint32_t> : k_update_walk<1, uint32_t>), g, b, 0, s, L,
+                             (const uint32_t*)labels, W, H, S, mw, mh, G, cpl, spixl);
+        break;
+      case plan::kSlicUpdate:  // the 16-bit copies: those the assignment before it wrote
+        if (st.LT == 16)
+          hipLaunchKernelGGL((st.UT == 4 ? k_update<4, uint16_t> : k_update<1, uint16_t>), g, b, 0, s, L,
+                             (const uint16_t*)scratch, W, H, S, mw, mh, G, cpl, spixl);
+        else
+          hipLaunchKernelGGL(st.UT == 4 ? k_update<4> : k_update<1>, g, b, 0, s, L, (const uint32_t*)labels, W, H, S,
+                             mw, mh, G, cpl, spixl);
+        break;
+      case plan::kSlicSuppress:
+        if (st.to_scratch)
+          hipLaunchKernelGGL(k_suppress, g, b, 0, s, (const uint32_t*)labels, (uint32_t*)scratch, W, H);
+        else
+          hipLaunchKernelGGL(k_suppress, g, b, 0, s, (const uint32_t*)scratch, labels, W, H);
+        break;
     }
-    MVS_LAUNCH_CHECK("k_update_walk");
-    return 0;
+    MVS_LAUNCH_CHECK(names[st.kernel]);
   }
-  if (lb16 && (long)mw * mh <= 65536) {  // the 16-bit copy the previous launch_assign wrote
-    auto k16 = G > 4 ? k_update<4, uint16_t> : k_update<1, uint16_t>;
-    hipLaunchKernelGGL(k16, dim3((mw * mh + 3) / 4, V), dim3(256), 0, s, (const float4*)lab, lb16, W, H, S, mw, mh,
-                       G, cpl, spixl);
-  } else {
-    hipLaunchKernelGGL(G > 4 ? k_update<4> : k_update<1>, dim3((mw * mh + 3) / 4, V), dim3(256), 0, s,
-                       (const float4*)lab, labels, W, H, S, mw, mh, G, cpl, spixl);
-  }
-  MVS_LAUNCH_CHECK("k_update");
-  return 0;
-}
-
-int launch_suppress(hipStream_t s, const uint32_t* in, uint32_t* out, int V, int W, int H) {
-  hipLaunchKernelGGL(k_suppress, dim3((W + 255) / 256, H, V), dim3(256), 0, s, in, out, W, H);
-  MVS_LAUNCH_CHECK("k_suppress");
   return 0;
 }
 

@@ -128,7 +128,7 @@ def main():
     for r in rows[:8]:
         print(f"{short(r[0]):40s} calls={r[1]:5d} avg={r[3]:9.3f} us  {r[4]:6.2f}%")
     for k in sorted(pmc):
-        if k.split("<")[0] in ("k_wta", "k_ncc_volume", "k_ncc_mfma", "k_cvt", "k_update_tiles", "k_assign", "k_box_stats"):
+        if k.split("<")[0] in ("k_wta", "k_ncc_volume", "k_ncc_mfma", "k_cvt", "k_assign", "k_box_stats"):
             print(k, {a: round(b / 1e6, 2) for a, b in pmc[k].items() if "bytes" in a})
 
 

@@ -1,18 +1,20 @@
-// Cases of the golden of the superpixel-sweep, SAD and filter launch planners
-// (tests/golden/launch_plans.txt) and the canonical line a planned launch
-// prints as.  Numbers only, no images: a case is a set of MVS_SWEEP_*,
-// MVS_SAD_* and MVS_FILTER_* knobs and a list of planner calls.
+// Cases of the golden of the SLIC, superpixel-sweep, SAD and filter launch
+// planners (tests/golden/launch_plans.txt) and the canonical line a planned
+// launch prints as.  Numbers only, no images: a case is a set of MVS_SLIC_*,
+// MVS_SWEEP_*, MVS_SAD_* and MVS_FILTER_* knobs and a list of planner calls.
 #pragma once
 #include <array>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
 
 namespace plancase {
 
-enum Kind { kSweep, kSad, kFilter };
+enum Kind { kSweep, kSad, kFilter, kSlic };
 struct Call {
   Kind kind = kSweep;
   int aw = 1, ah = 1, W = 96, H = 64, S = 8;
@@ -27,6 +29,7 @@ struct Call {
   bool allow_relayout = true;                 // sweep: false plans as after a failed scratch allocation
   int ya = 0, yb = -1;                        // filter: rows (yb < 0: H)
   bool band = false;
+  int no_iter = 5, edge = 0, search = 0, conn = 0;  // SLIC: mvs_slic_params
 };
 struct Case {
   std::string name;
@@ -108,6 +111,32 @@ inline void print_filter(FILE* f, int call, const char* kern, int FB, int NS, in
   fprintf(f, "c%d filter kern=%s FB=%d NS=%d ROWB=%d RM=%d inb=%d grid=%u,%u,%u block=%u PP=%ld off=%ld\n", call, kern,
           FB, NS, ROWB, RM, inb, grid[0], grid[1], grid[2], block, PP, proj_off);
 }
+// one SLIC launch: the kernel and its template coordinates, the grid and
+// block, the pointer arguments by role (lab, spixl, labels, scratch, null) and
+// the scalar arguments in the kernel's parameter order (xy, col: the float's
+// bits); colour weight, passed through untouched, is left out
+using SlicInt = std::pair<const char*, long>;
+using SlicBuf = std::pair<const char*, const char*>;
+inline void print_slic(FILE* f, int call, const char* kern, std::initializer_list<SlicInt> tmpl, unsigned gx,
+                       unsigned gy, unsigned gz, unsigned block, std::initializer_list<SlicBuf> bufs,
+                       std::initializer_list<SlicInt> args, const float* xy_col = nullptr) {
+  fprintf(f, "c%d slic %s", call, kern);
+  const char* sep = "<";
+  for (const SlicInt& t : tmpl) fprintf(f, "%s%s=%ld", sep, t.first, t.second), sep = ",";
+  fprintf(f, "%s grid=%u,%u,%u block=%u bufs=", tmpl.size() ? ">" : "", gx, gy, gz, block);
+  sep = "";
+  for (const SlicBuf& b : bufs) fprintf(f, "%s%s:%s", sep, b.first, b.second), sep = ",";
+  fprintf(f, " args=");
+  sep = "";
+  for (const SlicInt& a : args) fprintf(f, "%s%s:%ld", sep, a.first, a.second), sep = ",";
+  if (xy_col) {
+    uint32_t u[2];
+    memcpy(u, xy_col, sizeof u);
+    fprintf(f, ",xy:%08x,col:%08x", u[0], u[1]);
+  }
+  fprintf(f, "\n");
+}
+inline void print_slic_scratch(FILE* f, int call, size_t bytes) { fprintf(f, "c%d slic scratch=%zu\n", call, bytes); }
 
 // ---- the cases -----------------------------------------------------------------
 inline Call sweep(int aw, int ah, int nh, int nv, int D) {
@@ -126,6 +155,11 @@ inline Call filter(int V, int aw, int W = 100, int H = 70) {
   c.kind = kFilter, c.V = V, c.aw = aw, c.W = W, c.H = H;
   return c;
 }
+inline Call slic(int V, int W, int H, int S, int no_iter = 5) {
+  Call c;
+  c.kind = kSlic, c.V = V, c.W = W, c.H = H, c.S = S, c.no_iter = no_iter, c.D = 0;
+  return c;
+}
 
 // planner inputs of bench configuration C4's size (8 x 4 array, 1920 x 1080,
 // S = 32, 128 levels; the 3 x 3 box of neighbours), one call per launcher: --time
@@ -135,6 +169,8 @@ inline std::vector<Call> c4_calls() {
   s.z0 = 9, s.z1 = 10;  // an inner view: 8 neighbours
   return {w, s, f};
 }
+// the SLIC call of bench configuration C2 (5 views, 1920 x 1080, S = 32, 5 iterations): --time
+inline Call c2_slic_call() { return slic(5, 1920, 1080, 32, 5); }
 
 inline std::vector<Case> cases() {
   std::vector<Case> cs;
@@ -300,6 +336,60 @@ inline std::vector<Case> cases() {
     e3.ya = e3.yb = 20, e3.band = true;
     rows.insert(rows.end(), {e1, e2, e3});
     cs.push_back({"filter_rows", {}, rows});
+  }
+
+  // -- SLIC
+  {
+    // every S class at an image size (331 x 251) that is a multiple of neither 16 nor S; two views
+    std::vector<Call> sizes, iters, srch, knob, edge;
+    for (int S : {6, 8, 12, 16, 32, 40, 48, 64, 96}) sizes.push_back(slic(2, 331, 251, S));
+    cs.push_back({"slic_sizes", {}, sizes});
+    // no_iter 0, 1, 2, 5 on the walk path (S = 8), the 4-cell (32) and the 9-cell (48) tile path
+    for (int S : {8, 32, 48})
+      for (int n : {0, 1, 2, 5}) iters.push_back(slic(3, 331, 251, S, n));
+    cs.push_back({"slic_iters", {}, iters});
+    // search 1: k_assign<true>; the 9-cell tile kernel at S = 32 too
+    for (int S : {8, 40, 32, 48, 64})
+      for (int se : {0, 1})
+        for (int n : {0, 5}) {
+          Call c = slic(1, 331, 251, S, n);
+          c.search = se;
+          srch.push_back(c);
+        }
+    cs.push_back({"slic_search", {}, srch});
+    for (int S : {32, 64, 48, 8}) knob.push_back(slic(2, 331, 251, S));
+    knob.push_back(slic(2, 331, 251, 32, 0));
+    cs.push_back({"slic_tiles9", {{"MVS_SLIC_TILES9", "1"}}, knob});
+    cs.push_back({"slic_tiles9_other", {{"MVS_SLIC_TILES9", "2"}}, knob});
+    // 16-bit label copies need mw mh <= 65536: S = 6 at 1600 x 1480 is 267 x 247 = 65949 superpixels
+    // (UT = 1), S = 12 at 3200 x 2960 likewise (UT = 4); one superpixel fewer: 16-bit again
+    std::vector<Call> upd = {slic(3, 100, 70, 8),        slic(2, 331, 251, 40),      slic(1, 1600, 1480, 6),
+                             slic(1, 3200, 2960, 12),    slic(1, 1600, 1480, 6, 0),  slic(1, 1590, 1480, 6),
+                             slic(1, 1536, 1536, 6),     slic(2, 331, 251, 32),      slic(1, 100, 70, 8, 1)};
+    upd[2].conn = 1;
+    cs.push_back({"slic_update", {}, upd});
+    cs.push_back({"slic_update0", {{"MVS_SLIC_UPDATE", "0"}}, upd});
+    cs.push_back({"slic_update1", {{"MVS_SLIC_UPDATE", "1"}}, {upd[0], upd[1]}});
+    cs.push_back({"slic_update_nan", {{"MVS_SLIC_UPDATE", "walk"}}, {upd[0], upd[1]}});  // atoi: 0
+    cs.push_back({"slic_both_knobs", {{"MVS_SLIC_UPDATE", "0"}, {"MVS_SLIC_TILES9", "1"}}, {upd[1], upd[7]}});
+    // the edge step and the connectivity pass, both paths; no_iter = 0: the scratch is theirs alone
+    for (int S : {8, 32})
+      for (int e : {0, 1, 2})
+        for (int cn : {0, 1}) {
+          Call c = slic(2, 331, 251, S, e == 2 && cn ? 0 : 5);
+          c.edge = e, c.conn = cn;
+          edge.push_back(c);
+        }
+    Call hd = slic(1, 1920, 1080, 32);  // k_edge_store's grid: 8192 workgroups at most
+    hd.edge = 1;
+    edge.push_back(hd);
+    cs.push_back({"slic_edge_conn", {}, edge});
+    // W H = 2^27, the largest image: W H 16 = 2^31 is past the walk's and the
+    // 4-cell kernel's 32-bit offsets (k_update by size, the 9-cell kernel); just under it
+    cs.push_back({"slic_largest", {}, {slic(1, 16384, 8192, 40, 1), slic(1, 16384, 8192, 32, 1),
+                                       slic(1, 16384, 8192, 6, 1), slic(1, 16384, 8191, 40, 1),
+                                       slic(1, 16384, 8191, 32, 1)}});
+    cs.push_back({"slic_c2_c5", {}, {c2_slic_call(), slic(5, 1920, 1080, 40)}});
   }
   return cs;
 }

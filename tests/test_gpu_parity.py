@@ -551,6 +551,43 @@ def test_slic_tile_kernels(engine, monkeypatch, S, tiles9):
         assert_bits(sp[v][..., :7], osp[..., :7], f"spixl S={S} v{v}")
 
 
+_SLIC_ORACLE = {}
+
+
+def _slic_oracle(name, no_iter):
+    """orc.slic of every view of the case, computed once per (case, no_iter)."""
+    if (name, no_iter) not in _SLIC_ORACLE:
+        b = build(CASES[name])
+        _SLIC_ORACLE[name, no_iter] = [orc.slic(b["stack"][v], CASES[name]["S"], 0.6, no_iter)[1:]
+                                       for v in range(b["V"])]
+    return _SLIC_ORACLE[name, no_iter]
+
+
+@pytest.mark.parametrize("update", [None, "0"])
+@pytest.mark.parametrize("name", ["c3x1_s8", "c2x1_s40"])
+def test_slic_update_kernels(engine, monkeypatch, name, update):
+    """Both window-walk update kernels against the oracle, labels and centres
+    bit for bit after 1 and 5 iterations: k_update_walk (MVS_SLIC_UPDATE
+    unset) and k_update (MVS_SLIC_UPDATE=0: otherwise reached only by an image
+    of 2^27 pixels), which k_update_walk's header calls itself bit-identical
+    to.  c3x1_s8: G = 3, one tile per chunk (UT = 1); c2x1_s40: G = 57, four
+    (UT = 4); both read the 16-bit label copies.  The uint32_t label forms
+    need more than 65536 superpixels per view and are pinned by the planner's
+    golden only (tests/test_launch_plan_cpu.py)."""
+    if update is None:
+        monkeypatch.delenv("MVS_SLIC_UPDATE", raising=False)
+    else:
+        monkeypatch.setenv("MVS_SLIC_UPDATE", update)
+    c = CASES[name]
+    lab, _ = engine.cvt(dev(build(c)["stack"]))
+    for no_iter in (1, 5):
+        sp, lb = engine.slic(lab, c["S"], 0.6, no_iter)
+        sp, lb = sp.cpu().numpy(), as_u32(lb)
+        for v, (osp, olb) in enumerate(_slic_oracle(name, no_iter)):
+            assert_bits(lb[v], olb, f"labels it{no_iter} v{v}")
+            assert_bits(sp[v][..., :7], osp[..., :7], f"spixl it{no_iter} v{v}")
+
+
 @pytest.mark.parametrize("kind", ["flat", "ramp", "checker"])
 def test_slic_ties(engine, kind):
     """Images built so that many pixels sit at (near-)equal distance from two
