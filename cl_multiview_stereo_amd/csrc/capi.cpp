@@ -72,6 +72,11 @@ int upload_meta(mvs_ctx* c, const mvs_array* a) {
 
 bool bad_dims(int W, int H) { return W <= 0 || H <= 0 || (long)W * H > (1L << 31) / 16; }
 
+// SLIC's own bound on each dimension (include/mvs.h at mvs_slic_d).  The update kernels form a tile's sums
+// of member x and of member y as one integer converted to float where the reference runs a float tree; the
+// two agree only while every sum is exact in float: at most 256 members of x <= 65535, 16,776,960 < 2^24.
+bool bad_slic_dims(int W, int H) { return W > 65536 || H > 65536; }
+
 struct DevBuf {
   void* p = nullptr;
   ~DevBuf() {
@@ -211,7 +216,7 @@ int mvs_grid_d(mvs_ctx* c, const float* lab, int V, int W, int H, int S, float* 
 
 int mvs_slic_d(mvs_ctx* c, float* lab, int V, int W, int H, const mvs_slic_params* p, float* spixl,
                uint32_t* labels) {
-  if (!c || !lab || !spixl || !labels || !p || V <= 0 || bad_dims(W, H))
+  if (!c || !lab || !spixl || !labels || !p || V <= 0 || bad_dims(W, H) || bad_slic_dims(W, H))
     return mvs::arg_fail("mvs_slic_d: bad arguments");
   if (p->struct_size != sizeof(mvs_slic_params))
     return mvs::arg_fail("mvs_slic_d: struct_size != sizeof(mvs_slic_params) (caller built against another mvs.h)");
@@ -558,7 +563,8 @@ int mvs_remove_inconsistency_rows_d(mvs_ctx* c, int V, int W, int H, int array_w
 // ---- host-pointer API (reference stage methods) ----------------------------------
 int mvs_do_super_pixel_seg(mvs_ctx* c, const uint8_t* rgbx, int W, int H, const mvs_slic_params* p, float* lab,
                            float* spixl, uint32_t* labels) {
-  if (!c || !rgbx || !p || bad_dims(W, H) || p->spixl_size <= 0) return mvs::arg_fail("mvs_do_super_pixel_seg: bad arguments");
+  if (!c || !rgbx || !p || bad_dims(W, H) || bad_slic_dims(W, H) || p->spixl_size <= 0)
+    return mvs::arg_fail("mvs_do_super_pixel_seg: bad arguments");
   size_t P = (size_t)W * H;
   int mw = mvs::map_dim(W, p->spixl_size), mh = mvs::map_dim(H, p->spixl_size);
   size_t M = (size_t)mw * mh;

@@ -282,7 +282,9 @@ __global__ __launch_bounds__(256) void k_assign(const float4* __restrict__ lab, 
   }
   __syncthreads();
   if (col >= W) return;
-  // n / S as a multiply-high with M = ceil(2^32 / S): exact for n < 2^16, S <= 96
+  // n / S as a multiply-high with M = ceil(2^32 / S) = (2^32 + r) / S, r < S: n M / 2^32 = n / S + n r / (2^32 S),
+  // whose last term stays below 1 / S -- the floor is that of n / S -- for n < 2^32 / S: every n <= 65536 + S
+  // that mvs_slic_d's W, H <= 65536 lets through, S <= 96
   const unsigned M = 0xffffffffu / (unsigned)S + 1u;
   auto divS = [&](int n) { return (int)__umulhi((unsigned)n, M); };
   const int cxg = divS(col), dX = divS(col + S / 2) - cxg;
@@ -515,7 +517,8 @@ __global__ __launch_bounds__(256) void k_update(const float4* __restrict__ lab, 
       if (__any(any)) {
         const uint32_t q = wave_sum_u32(pk[0], pk[1], pk[2], pk[3]);
         const int cnt = (q >> 24) ? (int)(q >> 24) : 256;
-        r[0] = (float)((int)(q & 0xfffu) + cnt * bx[u]);  // = the sum of member x: exact below 2^24
+        // = the sum of member x, the reference's float tree while below 2^24 (mvs_slic_d rejects W or H above 65536)
+        r[0] = (float)((int)(q & 0xfffu) + cnt * bx[u]);
         r[1] = (float)((int)((q >> 12) & 0xfffu) + cnt * by[u]);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) r[2 + ch] = wave_tree(v[0][ch], v[1][ch], v[2][ch], v[3][ch]);
@@ -643,7 +646,8 @@ __global__ __launch_bounds__(256) void k_update_walk(const float4* __restrict__ 
         }
         const uint32_t q = wave_sum_u32(pk[0], pk[1], pk[2], pk[3]);
         const int cnt = (q >> 24) ? (int)(q >> 24) : 256;
-        rx = (float)((int)(q & 0xfffu) + cnt * bxs[u]);  // the sum of member x: exact below 2^24
+        // the sum of member x: exact below 2^24 (mvs_slic_d rejects W or H above 65536)
+        rx = (float)((int)(q & 0xfffu) + cnt * bxs[u]);
         ry = (float)((int)((q >> 12) & 0xfffu) + cnt * bys[u]);
         rn = (float)cnt;
         float sc[3];
@@ -730,7 +734,7 @@ __global__ __launch_bounds__(256) void k_assign_tiles(const float4* __restrict__
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const unsigned M = 0xffffffffu / (unsigned)S + 1u;  // n / S, exact for n < 2^16, S <= 96
+  const unsigned M = 0xffffffffu / (unsigned)S + 1u;  // n / S, exact for n < 2^32 / S (k_assign; mvs_slic_d: n <= 65536 + S)
   auto divS = [&](int n) { return (int)__umulhi((unsigned)n, M); };
 #pragma unroll
   for (int m = 0; m < 4; m++) {
@@ -785,7 +789,8 @@ __global__ __launch_bounds__(256) void k_assign_tiles(const float4* __restrict__
       }
       float r[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if (__any(any)) {
-        // x, y and count are integers whose float trees are exact (sums < 2^24), so
+        // x, y and count are integers whose float trees are exact (sums < 2^24:
+        // mvs_slic_d rejects W or H above 65536), so
         // they come from one integer tree of packed tile-local fields: sum of
         // x - 16 TX (<= 3840, bits 0-11), of y - 16 TY (bits 12-23) and the count
         // (bits 24-31; 256 wraps to 0, and a tree only runs with a member present)
@@ -1034,6 +1039,7 @@ __global__ __launch_bounds__(256) void k_assign_tiles4(const float4* __restrict_
       const int cnt = (Q >> 24) ? (int)(Q >> 24) : 256;  // present: at least one member
       const bool qs = lane == 0 || (lane == 32 && two);
       const int ob = qs ? (lane == 0 ? base[0] : base[1]) * 4 : kOob;
+      // the sums of member x and y, the reference's float trees while below 2^24 (mvs_slic_d rejects W or H above 65536)
       const float fx = (float)((int)(Q & 0xfffu) + cnt * 16 * TX), fy = (float)((int)((Q >> 12) & 0xfffu) + cnt * 16 * TY);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fx), rpt, ob, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fy), rpt, qs ? ob + 4 : kOob, 0, 0);

@@ -123,7 +123,13 @@ int mvs_cvt_d(mvs_ctx* ctx, const uint8_t* rgbx, int V, int W, int H, float* lab
  * lab is read only, except with p->edge_enable == 1, where the reference's
  * edge step overwrites it (as clSLIC's lab_img_dev).  Every spixl word is
  * written; s7 (disparity, untouched by the reference's SLIC on its zeroed
- * buffer) is set to 0. */
+ * buffer) is set to 0.
+ * W <= 65536 and H <= 65536 (otherwise the "bad arguments" failure, from
+ * mvs_do_super_pixel_seg as well): the centre update sums a 16 x 16 tile's
+ * member x and y as one integer converted to float, which equals the
+ * reference's float tree only while that sum is exact in float -- 256 members
+ * of x <= 65535 stay below 2^24 (likewise y).  The kernels' multiply-high
+ * division by S, exact below 2^32 / S, is far inside its range there. */
 int mvs_slic_d(mvs_ctx* ctx, float* lab, int V, int W, int H, const mvs_slic_params* p,
                float* spixl, uint32_t* labels);
 

@@ -309,13 +309,36 @@ def suppress(labels):
     return out
 
 
-def slic_from_lab(lab, S, weight=0.6, no_iter=5, enforce_connectivity=False, search=0):
-    """clSLIC::do_super_pixel_seg minus its cvt, on one view's Lab."""
+def apply_edge(lab, edge_mag, S, spixl):
+    """apply_edge_alternative on ONE view: a copy of spixl with each centre moved
+    to its 8-neighbour of least edge value (orc_apply_edge)."""
+    lab = np.ascontiguousarray(lab, np.float32)
+    e = np.ascontiguousarray(edge_mag, np.float32)
+    H, W = lab.shape[:2]
+    sp = np.array(spixl, np.float32, copy=True, order="C")
+    lib().orc_apply_edge(_p(lab, f32p), _p(e, f32p), W, H, S, _p(sp, f32p))
+    return sp
+
+
+def slic_from_lab(lab, S, weight=0.6, no_iter=5, enforce_connectivity=False, search=0, edge_enable=0):
+    """clSLIC::do_super_pixel_seg minus its cvt, on one view's Lab.
+    edge_enable as orc_edge_step: 1 overwrites L, a and b with the edge
+    magnitude (the assignments then run on that image, returned as a third
+    value), 2 moves the centres to their least-edge neighbour.  -> (spixl,
+    labels), or (spixl, labels, lab) with edge_enable = 1."""
     sp = init_centers(lab, S)
+    if edge_enable == 1:
+        e = edge(lab)
+        lab = np.array(lab, np.float32, copy=True, order="C")
+        lab[..., 0] = lab[..., 1] = lab[..., 2] = e
+    elif edge_enable == 2:
+        sp = apply_edge(lab, edge(lab), S, sp)
+    elif edge_enable != 0:
+        raise ValueError("edge_enable must be 0, 1 or 2")
     lb = assign(lab, sp, S, weight, search)
     for _ in range(no_iter):
         sp = update(lab, lb, S)
         lb = assign(lab, sp, S, weight, search)
     if enforce_connectivity:
         lb = suppress(suppress(lb))
-    return sp, lb
+    return (sp, lb, lab) if edge_enable == 1 else (sp, lb)

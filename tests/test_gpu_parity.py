@@ -572,8 +572,8 @@ def test_slic_update_kernels(engine, monkeypatch, name, update):
     of 2^27 pixels), which k_update_walk's header calls itself bit-identical
     to.  c3x1_s8: G = 3, one tile per chunk (UT = 1); c2x1_s40: G = 57, four
     (UT = 4); both read the 16-bit label copies.  The uint32_t label forms
-    need more than 65536 superpixels per view and are pinned by the planner's
-    golden only (tests/test_launch_plan_cpu.py)."""
+    need more than 65536 superpixels per view: tests/test_gpu_slic_content.py
+    (l32_s6, l32_s12) runs them."""
     if update is None:
         monkeypatch.delenv("MVS_SLIC_UPDATE", raising=False)
     else:
