@@ -40,6 +40,7 @@ Tuning plan_tuning() {
   t.sweep_transpose = num("MVS_SWEEP_TRANSPOSE", 2);
   t.sweep_hz = num("MVS_SWEEP_HZ", 1) != 0;
   t.sweep_ring = num("MVS_SWEEP_RING", 1) != 0;
+  t.sweep_ring_fast = num("MVS_SWEEP_RING_FAST", 1) != 0;
   if (const char* kv = getenv("MVS_SAD_KERNEL")) {
     t.sad_kernel = kv;
     t.sad_named = true;

@@ -61,6 +61,9 @@ struct Tuning {
   int sweep_transpose = 2;  // MVS_SWEEP_TRANSPOSE: 0 row-major gathers only, 1 vertical neighbours re-laid, 2 diagonal ones too
   bool sweep_hz = true;     // MVS_SWEEP_HZ=0: the general form where HZ would run
   bool sweep_ring = true;   // MVS_SWEEP_RING=0: the HZ gathers where the ring form would run
+  // MVS_SWEEP_RING_FAST=0: the ring kernel's general row-steps where its whole-window path would run (A/B; a
+  // kernel argument, no part of the plan)
+  bool sweep_ring_fast = true;
   // MVS_SAD_KERNEL: "sys8x2", "sys8", "gather"; unset: 16-level chunks, else
   // 8-level chunks (taller bands: vertical neighbours), else the gather kernel.
   // A band variant named explicitly never falls back (MVS_E_UNSUPPORTED), so a

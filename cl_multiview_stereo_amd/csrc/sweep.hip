@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "mvs_internal.h"
@@ -82,12 +83,8 @@ __global__ __launch_bounds__(256) void k_boundary(const float* __restrict__ spix
   if (lane == 0) *(uint2*)(rep + 8 * (z * M + s)) = make_uint2(w, hi);
 }
 
-// 16-byte LDS-DMA: lane l's 16 bytes land at dst + 16 l (dst wave-uniform)
+// the destination of a 16-byte LDS-DMA: lane l's 16 bytes land at dst + 16 l (dst wave-uniform)
 typedef __attribute__((address_space(3))) void* lds_vptr_t;
-typedef const __attribute__((address_space(1))) void* glb_vptr_t;
-__device__ __forceinline__ void glds16(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds((glb_vptr_t)src, (lds_vptr_t)dst, 16, 0, 0);
-}
 
 // ---- initial_depth_estimation_v2, clcode.cl:972-1069 ----------------------
 struct SweepArgs {
@@ -312,6 +309,15 @@ __global__ __launch_bounds__(256) void k_sweep_spixl(const float4* __restrict__ 
 // columns: 2 (S - 1) + 2 + |dx| x the levels' range over any 64 consecutive
 // levels (stx <= (S - 1) / 2), else the HZ gathers.
 // (kSwU: launch_plan.h, shared with the planner)
+// What a (pass, neighbour) fixes is set up once for its five rows: the
+// window, the lane's shift and the staging source -- the neighbour view's
+// plane as a buffer, so a row's piece is a scalar offset beside one lane
+// offset.  Where all 25 reference taps are inside and the window is whole
+// (no lane's tap column leaves the image: a scalar test on the window's
+// ends), the whole-window path runs: five tap addresses per lane for the
+// neighbour, no clamp, no outside marker, three adds per tap in the chain.
+// Every other (pass, neighbour) takes the general row-steps, and fast = 0
+// (MVS_SWEEP_RING_FAST=0) sends all of them there.
 __device__ __forceinline__ void wait_vm(int n) {  // s_waitcnt vmcnt(n), n in [0, 6]
   switch (n) {
     case 0: __builtin_amdgcn_s_waitcnt(0x0f70); break;
@@ -332,12 +338,42 @@ __device__ __forceinline__ float wave_min_f(float v) {
   v = fminf(v, __shfl_xor(v, 1));
   return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
+// tap_acc for a tap known to be inside: val = ((val + 30) - 30) + ad
+__device__ __forceinline__ float tap_acc_in(float val, float ad) {
+  float t;
+  asm("v_add_f32 %0, 0x41f00000, %1" : "=v"(t) : "v"(val));
+  asm("v_add_f32 %0, 0xc1f00000, %1" : "=v"(t) : "v"(t));
+  asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(t), "v"(ad));
+  return t;
+}
+// a row's 5 taps from the ring slot at byte OFF past the lane's addresses and
+// the row's 5 reference colours, closed by lgkmcnt(0) (see the general path's reads)
+template <int OFF>
+__device__ __forceinline__ void ring_taps5(const unsigned (&ra)[5], unsigned rb, u32x3 (&Bv)[5], f32x4 (&Av)[5]) {
+  asm volatile(
+      "ds_read_b96 %0, %10 offset:%16\n\t"
+      "ds_read_b96 %1, %11 offset:%16\n\t"
+      "ds_read_b96 %2, %12 offset:%16\n\t"
+      "ds_read_b96 %3, %13 offset:%16\n\t"
+      "ds_read_b96 %4, %14 offset:%16\n\t"
+      "ds_read_b128 %5, %15\n\t"
+      "ds_read_b128 %6, %15 offset:80\n\t"
+      "ds_read_b128 %7, %15 offset:160\n\t"
+      "ds_read_b128 %8, %15 offset:240\n\t"
+      "ds_read_b128 %9, %15 offset:320\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(Bv[0]), "=&v"(Bv[1]), "=&v"(Bv[2]), "=&v"(Bv[3]), "=&v"(Bv[4]), "=&v"(Av[0]), "=&v"(Av[1]),
+        "=&v"(Av[2]), "=&v"(Av[3]), "=&v"(Av[4])
+      : "v"(ra[0]), "v"(ra[1]), "v"(ra[2]), "v"(ra[3]), "v"(ra[4]), "v"(rb), "i"(OFF)
+      : "memory");
+}
 template <int WPS>
 __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restrict__ lab, float* __restrict__ spixl,
                                                           const uint8_t* __restrict__ rep,
                                                           const float* __restrict__ levels, const int* __restrict__ vs,
-                                                          const int* __restrict__ sn, SweepArgs a) {
+                                                          const int* __restrict__ sn, SweepArgs a, int fast) {
   constexpr int SPB = 4 / WPS;
+  constexpr unsigned kSlotB = kSwU * 16u;            // bytes of a ring slot
   __shared__ __align__(16) float4 ring[4][2][kSwU];  // per wave: two row slots
   __shared__ float4 refc[SPB][25];
   __shared__ int rxr[SPB][5], ryr[SPB][5];           // tap columns (i) and rows (j), possibly outside
@@ -381,9 +417,9 @@ __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restri
   const unsigned vm = __builtin_amdgcn_readfirstlane(rvm[slot]);
   int xr[5], yr[5];
 #pragma unroll
-  for (int q = 0; q < 5; q++) {
-    xr[q] = rxr[slot][q];
-    yr[q] = ryr[slot][q];
+  for (int q = 0; q < 5; q++) {  // (scalars: the window, the row offsets and the tap columns are scalar arithmetic)
+    xr[q] = __builtin_amdgcn_readfirstlane(rxr[slot][q]);
+    yr[q] = __builtin_amdgcn_readfirstlane(ryr[slot][q]);
   }
   // the union of the inside taps' columns (any row), and the rows holding one
   int xlo = 1 << 30, xhi = -(1 << 30);
@@ -394,11 +430,7 @@ __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restri
       xhi = max(xhi, xr[q]);
     }
   const int rx = z % a.aw;  // (every neighbour in the reference's camera row)
-  // the taps' columns (-2^30 outside), uniform, and the LDS byte addresses of
-  // this wave's ring and this superpixel's reference colours
-  int rcol[25];
-#pragma unroll
-  for (int t = 0; t < 25; t++) rcol[t] = __float_as_int(refc[slot][t].w);  // (VGPRs: the LDS caps the waves, not these)
+  // the LDS byte addresses of this wave's ring and this superpixel's reference colours
   const unsigned ring_base = (unsigned)(uintptr_t)(lds_vptr_t)&ring[w][0][0];
   const unsigned refc_base = (unsigned)(uintptr_t)(lds_vptr_t)&refc[slot][0];
   const int nn = sn[z];
@@ -411,55 +443,118 @@ __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restri
     // the pass's level range: (int)(d dx) is monotone in d, so a neighbour's
     // shift range comes from its ends
     const float dlo = wave_min_f(d), dhi = -wave_min_f(-d);
-    // the staging window of neighbour n: columns [ulo, ulo + U) of its view
-    auto window = [&](int n, int& ulo, int& U, int& sh) {
+    // The neighbour being staged (rows k + 2), set up once per (pass,
+    // neighbour): its view's plane, this lane's shift, the staging window --
+    // columns [ulo, ulo + U) of the view -- the lane's byte offset within a
+    // piece, and whether the window is whole: no lane's tap column leaves the
+    // image (the window's ends are the extreme lanes' extreme columns, so one
+    // scalar test speaks for all 64 lanes) and the slot holds it.
+    const float4* pl_s = lab;
+    int ulo_s = 0, U_s = 0, sh_s = 0, vo_s = 0;
+    bool whole_s = false;
+    auto open_nb = [&](int n) {
       const int view = vs[a.V * z + n];
       const float fdx = (float)(view % a.aw - rx);
-      sh = (int)(d * fdx);  // exact (the launcher checked the levels)
+      sh_s = (int)(d * fdx);  // exact (the launcher checked the levels)
       const int s0 = (int)(dlo * fdx), s1 = (int)(dhi * fdx);
       const int shmin = min(s0, s1), shmax = max(s0, s1);
-      ulo = max(xlo - shmax, 0);
-      U = min(xhi - shmin, a.W - 1) - ulo + 1;
+      const int lo = xlo - shmax, hi = xhi - shmin;
+      ulo_s = max(lo, 0);
+      const int U = min(hi, a.W - 1) - ulo_s + 1;
+      whole_s = lo >= 0 && hi < a.W && U <= kSwU;
+      U_s = min(U, kSwU);  // (the launcher's bound makes this a no-op; never past the slot)
+      vo_s = 16 * min(lane, max(U_s, 1) - 1);  // U < 64: lanes past U re-read column U - 1
+      pl_s = lab + (long)view * P;
     };
-    // stage row k = 5 n + j into slot k & 1; returns its LDS-DMA pieces (0:
-    // nothing staged -- no inside tap on the row, an empty or too wide window)
-    auto stage = [&](int n, int j, int k, int ulo, int U) -> int {
-      if (U <= 0 || !((vm >> j) & 0x108421u)) return 0;
-      U = min(U, kSwU);  // (the launcher's bound makes this a no-op; never past the slot)
-      const int view = vs[a.V * z + n];
-      const float4* row = lab + (long)view * P + (long)yr[j] * a.W + ulo;
-      const int np = (U + 63) >> 6;
+    // stage row j of that neighbour into slot sl; returns its LDS-DMA pieces
+    // (0: nothing staged -- no inside tap on the row, or an empty window).
+    // The view's plane is the buffer, the row and the piece a scalar offset.
+    auto stage = [&](int j, int sl) -> int {
+      if (U_s <= 0 || !((vm >> j) & 0x108421u)) return 0;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)pl_s, 0, (int)(P * 16), 0x00020000);
+      const int ro = (yr[j] * a.W + ulo_s) * 16;
+      const int np = (U_s + 63) >> 6;
       for (int q = 0; q < np; q++) {
-        const int c0 = U >= 64 ? min(q * 64, U - 64) : 0;  // the last piece ends at U (U < 64: lanes past U re-read column U - 1)
-        glds16(row + min(c0 + lane, U - 1), &ring[w][k & 1][c0]);
+        const int c0 = U_s >= 64 ? min(q * 64, U_s - 64) : 0;  // the last piece ends at U
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_vptr_t)&ring[w][sl][c0], 16, vo_s, ro + 16 * c0, 0, 0);
       }
       return np;
     };
     float mn = 1000000.0f;
     if (nn > 0) {
-      int ulo0, U0, sh0;
-      window(0, ulo0, U0, sh0);
-      int pcn = stage(0, 0, 0, ulo0, U0);  // pieces of the row after the one computed next
-      pcn = stage(0, 1, 1, ulo0, U0);
-      int ulo_c = ulo0, sh_c = sh0;  // the neighbour being computed
-      int ulo_s = ulo0, U_s = U0;              // the neighbour being staged (rows k + 2)
+      open_nb(0);
+      int pcn = stage(0, 0);  // pieces of the row after the one computed next
+      pcn = stage(1, 1);
+      int ulo_c = ulo_s, sh_c = sh_s;  // the neighbour being computed
+      bool whole_c = whole_s;
       for (int n = 0; n < nn; n++) {
+        const int par = n & 1;  // row k = 5 n + j sits in slot (n + j) & 1
+        // after row j's reads: stage row k + 2 into the slot they left (the
+        // next neighbour's rows 0 and 1 from j = 3 on)
+        auto stage_ahead = [&](int j) {
+          int pc2 = 0;
+          if (j < 3 || n + 1 < nn) {
+            if (j == 3) open_nb(n + 1);
+            pc2 = stage(j < 3 ? j + 2 : j - 3, (par + j) & 1);
+          }
+          pcn = pc2;
+        };
+        // The whole-window path, chosen per (pass, neighbour) by scalar
+        // tests: all 25 reference taps inside and the window whole, so every
+        // tap of every lane is inside.  A lane's five tap addresses are set
+        // once (the slot is the read's immediate offset, hence the two
+        // parities), a row-step is its 10 LDS reads and 25 VALU, and the chain
+        // runs without the outside marker's compare and select.
+        auto whole_rows = [&](auto PAR) -> float {
+          unsigned ra[5];
+#pragma unroll
+          for (int i = 0; i < 5; i++) ra[i] = ring_base + (unsigned)(xr[i] - sh_c - ulo_c) * 16u;
+          float ad[25];
+#pragma unroll
+          for (int j = 0; j < 5; j++) {
+            wait_vm(5 * n + j + 1 < 5 * nn ? pcn : 0);  // row k landed (row k + 1 may still be in flight)
+            u32x3 Bv[5];
+            f32x4 Av[5];
+            const unsigned rb = refc_base + (unsigned)j * 16u;
+            if ((decltype(PAR)::value + j) & 1)
+              ring_taps5<(int)kSlotB>(ra, rb, Bv, Av);
+            else
+              ring_taps5<0>(ra, rb, Bv, Av);
+            stage_ahead(j);
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+              const int t = 5 * i + j;
+              ad[t] = tap_ad(make_float4(Av[i].x, Av[i].y, Av[i].z, 0.f), Bv[i]);
+            }
+          }
+          float val = 0.0f;
+#pragma unroll
+          for (int t = 0; t < 25; t++) val = tap_acc_in(val, ad[t]);
+          return val;
+        };
+        if (fast && vm == 0x1ffffffu && whole_c) {
+          const float val = par ? whole_rows(std::integral_constant<int, 1>()) : whole_rows(std::integral_constant<int, 0>());
+          mn = val < mn ? val : mn;
+          if (n + 1 < nn) ulo_c = ulo_s, sh_c = sh_s, whole_c = whole_s;
+          continue;
+        }
         float ad[25];
 #pragma unroll
         for (int j = 0; j < 5; j++) {
           const int k = 5 * n + j;
           wait_vm(k + 1 < 5 * nn ? pcn : 0);  // row k landed (row k + 1 may still be in flight)
-          // the row's 5 taps: their columns (refc .w), then the 5 ring reads
-          // and the 5 reference colours in one asm block closed by
-          // lgkmcnt(0) -- the compiler would put vmcnt(0) (every LDS-DMA in
-          // flight, row k + 1's included) before plain LDS reads here
+          // the row's 5 taps: their columns (-2^30 for a reference tap
+          // outside), then the 5 ring reads and the 5 reference colours in
+          // one asm block closed by lgkmcnt(0) -- the compiler would put
+          // vmcnt(0) (every LDS-DMA in flight, row k + 1's included) before
+          // plain LDS reads here
           int xp[5];
           unsigned ra[5];
 #pragma unroll
           for (int i = 0; i < 5; i++) {
-            xp[i] = rcol[i * 5 + j] - sh_c;
+            xp[i] = ((vm >> (5 * i + j)) & 1u ? xr[i] : -(1 << 30)) - sh_c;
             const bool in = (unsigned)xp[i] < (unsigned)a.W;
-            ra[i] = ring_base + (unsigned)(k & 1) * (kSwU * 16u) + (in ? (unsigned)(xp[i] - ulo_c) * 16u : 0u);
+            ra[i] = ring_base + (unsigned)(k & 1) * kSlotB + (in ? (unsigned)(xp[i] - ulo_c) * 16u : 0u);
           }
           const unsigned rb = refc_base + (unsigned)j * 16u;
           u32x3 Bv[5];
@@ -486,28 +581,14 @@ __global__ __launch_bounds__(256) void k_sweep_spixl_ring(const float4* __restri
             const float v = tap_ad(make_float4(Av[i].x, Av[i].y, Av[i].z, 0.f), Bv[i]);
             ad[5 * i + j] = in ? v : -1.0f;
           }
-          // stage row k + 2 (the next neighbour's rows 0 and 1 from j = 3 on)
-          const int k2 = k + 2;
-          int pc2 = 0;
-          if (k2 < 5 * nn) {
-            const int n2 = k2 / 5, j2 = k2 - 5 * n2;
-            if (j2 == 0) {
-              int sh2;
-              window(n2, ulo_s, U_s, sh2);
-            }
-            pc2 = stage(n2, j2, k2, ulo_s, U_s);
-          }
-          pcn = pc2;
+          stage_ahead(j);
         }
         float val = 0.0f;
 #pragma unroll
         for (int t = 0; t < 25; t++) val = tap_acc(val, ad[t], ad[t] >= 0.0f);
         mn = val < mn ? val : mn;
-        if (n + 1 < nn) {  // the next neighbour's window (staged from j = 3 of this one)
-          ulo_c = ulo_s;
-          const int view = vs[a.V * z + n + 1];
-          sh_c = (int)(d * (float)(view % a.aw - rx));
-        }
+        // the next neighbour's window (staged from j = 3 of this one)
+        if (n + 1 < nn) ulo_c = ulo_s, sh_c = sh_s, whole_c = whole_s;
       }
     }
     if (act && mn < best) {
@@ -1096,9 +1177,9 @@ int launch_sweep_spixl(mvs_ctx* ctx, int V, int W, int H, int S, const float* la
   const dim3 g(p.grid_x, p.grid_y);
   if (p.form == plan::kSweepHzRing) {
     static constexpr void (*ring[3])(const float4*, float*, const uint8_t*, const float*, const int*, const int*,
-                                     SweepArgs) = {k_sweep_spixl_ring<1>, k_sweep_spixl_ring<2>, k_sweep_spixl_ring<4>};
+                                     SweepArgs, int) = {k_sweep_spixl_ring<1>, k_sweep_spixl_ring<2>, k_sweep_spixl_ring<4>};
     hipLaunchKernelGGL(ring[p.wps == 1 ? 0 : p.wps == 2 ? 1 : 2], g, dim3(256), 0, s, (const float4*)lab, spixl, rep,
-                       levels, vs, sn, a);
+                       levels, vs, sn, a, (int)t.sweep_ring_fast);
     MVS_LAUNCH_CHECK("k_sweep_spixl_ring");
   } else {
     const bool half = p.lps == 32;
