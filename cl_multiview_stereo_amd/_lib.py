@@ -23,6 +23,7 @@ EXPORTS = [
     "mvs_do_super_pixel_seg", "mvs_do_initial_depth_estimation", "mvs_do_refinement", "mvs_do_consistency_filter",
     "mvs_init_state_range_l16_d", "mvs_propagate_l16_d", "mvs_spixl_to_image_l16_d",
     "mvs_wta_sub_d", "mvs_ncc_sub_range_d",
+    "mvs_sgm_d",
 ]
 
 

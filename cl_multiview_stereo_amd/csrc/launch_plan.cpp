@@ -371,5 +371,49 @@ FilterPlan plan_remove_incons(const Tuning& t, int V, int W, int H, int aw, int 
   return p;
 }
 
+SgmPlan plan_sgm(int W, int H, int D, int path) {
+  SgmPlan p;
+  if (W < 1 || H < 1 || D < 1 || path < 0 || path > 3) {
+    p.err = "sgm: bad dimensions or path";
+    return p;
+  }
+  if (D > kSgmMaxD) {
+    p.err = "sgm: more than 16384 levels";
+    return p;
+  }
+  const bool vertical = path >= 2;
+  p.rev = path & 1;
+  p.n = vertical ? H : W;
+  p.lines = vertical ? W : H;
+  if (vertical && D <= kSgmColumnsMaxD) {
+    p.form = kSgmColumns;
+    p.lpl = kSgmColumnsLpw;
+    p.waves = (D + kSgmColumnsLpw - 1) / kSgmColumnsLpw;
+    p.sstride = W;
+    p.lstride = 1;
+    p.grid = (unsigned)((W + 63) / 64);
+    // two buffers of {minimum, first, last} per wave and column; the kernel is built for 8 or 16 waves
+    p.lds = sizeof(float) * 2 * (p.waves <= 8 ? 8 : 16) * 3 * 64;
+  } else {
+    p.form = kSgmLanes;
+    p.sstride = vertical ? W : 1;
+    p.lstride = vertical ? 1 : W;
+    p.vec = !vertical;
+    if (D <= kSgmLanesOneWave) {
+      p.lpl = 1;
+      while (64 * p.lpl < D) p.lpl *= 2;
+      p.waves = 1;
+    } else {  // (the multi-wave kernel is held to 128 registers: no 16-byte pieces)
+      p.lpl = kSgmMaxLpl;
+      p.waves = (D + kSgmLanesOneWave - 1) / kSgmLanesOneWave;
+      p.vec = false;
+      p.lds = sizeof(float) * 2 * 16 * 3;  // two buffers of {minimum, first, last} per wave
+    }
+    p.grid = (unsigned)p.lines;
+  }
+  p.block = 64u * (unsigned)p.waves;
+  return p;
+}
+
 }  // namespace plan
 }  // namespace mvs

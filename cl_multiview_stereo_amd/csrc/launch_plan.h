@@ -196,5 +196,44 @@ struct FilterPlan {
 FilterPlan plan_remove_incons(const Tuning& t, int V, int W, int H, int aw, int z0, int z1, int ya, int yb,
                               bool band);
 
+// ---- launch_sgm (sgm.hip) ---------------------------------------------------
+// One path of the semi-global aggregation (include/mvs.h at mvs_sgm_d) over a
+// volume [D][H][W].  path: 0 left->right, 1 right->left (lines = rows, n = W
+// steps), 2 top->bottom, 3 bottom->top (lines = columns, n = H steps).
+//  * kSgmLanes, k_sgm_lanes<lpl, vec, waves > 1>: one workgroup of `waves`
+//    waves per line, every lane keeps lpl consecutive levels of the previous
+//    pixel in registers and walks the line; element i of line l of a level's
+//    plane is at l * lstride + i * sstride.  vec: the line is contiguous
+//    (sstride 1) and is read and written in aligned 16-byte pieces where a
+//    piece lies inside it (the launcher falls back to vec = false when vol and
+//    agg are not equally aligned mod 16 bytes).  One wave up to kSgmLanesOneWave
+//    levels; above, waves of 64 x 16 levels that meet in LDS once per step.
+//  * kSgmColumns, k_sgm_columns: vertical paths at D <= kSgmColumnsMaxD.  A
+//    workgroup takes 64 consecutive columns, lanes over x (a level's row piece
+//    is one coalesced 256 bytes), wave w keeps levels [lpl w, lpl (w + 1)) and
+//    the waves meet in LDS once per row (k_sgm_columns<512> up to 8 waves,
+//    <1024> above: the thread limit decides the register budget).
+// Vertical paths above kSgmColumnsMaxD levels take the lanes form with
+// sstride = W.
+constexpr int kSgmLanes = 0, kSgmColumns = 1;
+constexpr int kSgmMaxLpl = 16;                         // levels per lane of the lanes form: 1, 2, 4, 8, 16
+constexpr int kSgmLanesOneWave = 64 * kSgmMaxLpl;      // 1024 levels
+constexpr int kSgmColumnsLpw = 16;                     // levels per wave of the columns form
+constexpr int kSgmColumnsMaxD = 16 * kSgmColumnsLpw;   // 256 levels: 16 waves
+constexpr int kSgmMaxD = 16 * kSgmLanesOneWave;        // 16384 levels: 16 waves of the lanes form
+struct SgmPlan {
+  const char* err = nullptr;  // the argument error, if any
+  int form = kSgmLanes;
+  int lpl = 1;         // levels per lane (lanes form) or per wave (columns form)
+  int waves = 1;       // per workgroup
+  bool vec = false;    // lanes form: 16-byte pieces
+  int n = 0, lines = 0;  // steps of a path; rows or columns
+  int sstride = 0, lstride = 0;
+  bool rev = false;    // walk from the line's last element down
+  unsigned grid = 0, block = 0;
+  size_t lds = 0;      // static LDS of the kernel form, bytes
+};
+SgmPlan plan_sgm(int W, int H, int D, int path);
+
 }  // namespace plan
 }  // namespace mvs

@@ -1,0 +1,322 @@
+// Semi-global aggregation of a cost volume vol [D][H][W] along the four
+// axis-aligned paths (include/mvs.h at mvs_sgm_d; tests/sgm_ref.py).
+//
+// Definition, float32, every operation rounded (there is no multiply, so
+// nothing can fuse).  q is the pixel before p on the path:
+//   first pixel:  L(p, d) = vol[d][p]
+//   else:  m = min_k L(q, k)
+//          t = min(L(q, d), L(q, d-1) + P1 (d > 0), L(q, d+1) + P1 (d < D-1), m + P2)
+//          L(p, d) = (vol[d][p] + t) - m
+//   agg = ((L_b0 + L_b1) + L_b2) + L_b3 over the set bits of `paths`, in bit
+//   order: one launch per path, the first stores L, the others add to agg.
+// A level that does not exist (d-1 at 0, d+1 at D-1, the padding up to a lane's
+// or a wave's level count) is a state of +inf: inf + P1 drops out of the
+// minimum, and a padded level's own L stays +inf (m is finite, no NaN arises)
+// and is never stored.
+//
+// The layout decides the two forms (launch_plan.h at plan_sgm):
+//  * k_sgm_lanes: lanes over levels, one workgroup per line.  A lane keeps LPL
+//    consecutive levels of L(q, .) in registers, so d-1 and d+1 cross a lane
+//    boundary once per side (one shuffle each) and m is an in-wave reduction
+//    (DPP within the rows of 16 lanes, then four lane reads): no LDS and no
+//    barrier up to 1024 levels.  Above, the workgroup's waves leave {minimum,
+//    first, last} in LDS, double-buffered: one barrier per step.
+//    Along x a level's consecutive pixels are contiguous: VEC reads vol and
+//    reads-modifies-writes agg in aligned 16-byte pieces.  Which pixels share
+//    a piece depends on the level (the plane pitch H W need not be a multiple
+//    of 4) and on the row, so every (lane, level) has its own phase
+//    ph = (address of the line's first element / 4) mod 4: pixel x is element
+//    j = (x + ph) mod 4 of the piece of pixels x - j .. x - j + 3.  A piece
+//    inside the line is loaded when the walk enters it; when the walk leaves
+//    it, it is complete and is stored one step later, behind that step's
+//    loads (memory operations retire in order: a load issued behind a store
+//    waits for the store as well).  The pixels of a piece that crosses an end
+//    of the line are read and written one by one (the scalar head and tail).
+//  * k_sgm_columns: vertical paths at D <= 256.  Lanes over levels would read
+//    4 bytes per plane there, so the lanes lie over 64 consecutive columns (a
+//    level's row piece is one coalesced 256 bytes) and the levels are split
+//    over the waves, 16 per wave, unrolled in registers.  Per row the waves
+//    exchange {chunk minimum, first, last} per column through LDS,
+//    double-buffered: one barrier per row.  The next row's costs and agg
+//    are loaded before the waves meet and before this row's stores.
+// Plane bases are 64-bit, offsets within a plane 32-bit (W H <= 2^27).
+#include "mvs_internal.h"
+
+namespace mvs {
+namespace {
+
+#define SGM_INF __builtin_inff()
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_min(float v) {
+  const int o = __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false);
+  return fminf(v, __int_as_float(o));
+}
+
+// the minimum over the 64 lanes, in every lane (all lanes active)
+__device__ __forceinline__ float wave_min(float v) {
+  v = dpp_min<0xB1>(v);   // quad_perm [1,0,3,2]
+  v = dpp_min<0x4E>(v);   // quad_perm [2,3,0,1]
+  v = dpp_min<0x141>(v);  // row_half_mirror: the other quad of the 8
+  v = dpp_min<0x140>(v);  // row_mirror: the other half of the row of 16
+  const int b = __float_as_int(v);
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(b, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(b, 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(b, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(b, 48));
+  return fminf(fminf(r0, r1), fminf(r2, r3));
+}
+
+__device__ __forceinline__ float pick(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+__device__ __forceinline__ void put(float4& v, int j, float s) {
+  v.x = j == 0 ? s : v.x;
+  v.y = j == 1 ? s : v.y;
+  v.z = j == 2 ? s : v.z;
+  v.w = j == 3 ? s : v.w;
+}
+
+// One step of NL consecutive levels: L(q, .) in L -> L(p, .); up, dn = L(q, .)
+// of the level below the first and above the last (+inf: none).
+template <int NL>
+__device__ __forceinline__ void sgm_step(float (&L)[NL], const float (&c)[NL], float up, float dn, float m, float P1,
+                                         float P2) {
+  const float mp2 = m + P2;
+  float prev = up;
+#pragma unroll
+  for (int k = 0; k < NL; k++) {
+    const float cur = L[k], nxt = k + 1 < NL ? L[k + 1] : dn;
+    const float t = fminf(fminf(cur, prev + P1), fminf(nxt + P1, mp2));
+    L[k] = (c[k] + t) - m;
+    prev = cur;
+  }
+}
+
+template <int LPL, bool VEC, bool MW>
+__global__ __launch_bounds__(MW ? 1024 : 64) void k_sgm_lanes(const float* __restrict__ vol, float* __restrict__ agg,
+                                                              int D, long HW, int n, int sstride, int lstride,
+                                                              int rev, int acc, float P1, float P2) {
+  const int lane = threadIdx.x & 63;
+  const int d0 = (int)threadIdx.x * LPL;  // the lane's first level; levels >= D are padding and touch no memory
+  const long base = (long)d0 * HW + (long)((unsigned)blockIdx.x * (unsigned)lstride);
+  const float* vp = vol + base;
+  float* ap = agg + base;
+  const int jl = rev ? 3 : 0, js = rev ? 0 : 3;  // the element at which the walk enters / leaves a piece
+  float L[LPL];
+  float4 cv[LPL], av[LPL], pv[LPL];  // the piece of vol, of agg, and the completed piece of agg waiting to be stored
+  int ph[LPL], pxs[LPL];             // pxs: where pv goes (-1: nothing waits)
+#pragma unroll
+  for (int k = 0; k < LPL; k++) {
+    L[k] = SGM_INF;
+    cv[k] = av[k] = pv[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    pxs[k] = -1;
+    ph[k] = VEC ? (int)(((uintptr_t)(vp + (long)k * HW) >> 2) & 3) : 0;  // (vol and agg: equal mod 16 bytes)
+  }
+  for (int i = 0; i < n; i++) {
+    const int x = rev ? n - 1 - i : i;
+    float c[LPL];
+    if (VEC) {
+      // the pieces this step enters, every level's before anything waits for one
+#pragma unroll
+      for (int k = 0; k < LPL; k++) {
+        const int j = (x + ph[k]) & 3, xs = x - j;
+        if (d0 + k < D && j == jl && xs >= 0 && xs + 3 < n) {
+          cv[k] = *(const float4*)(vp + (long)k * HW + xs);
+          if (acc) av[k] = *(const float4*)(ap + (long)k * HW + xs);
+        }
+      }
+      // then the pieces the last step completed, behind the loads: issued in front of them, the loads' data would
+      // wait for these stores as well
+#pragma unroll
+      for (int k = 0; k < LPL; k++) {
+        if (pxs[k] >= 0) {
+          *(float4*)(ap + (long)k * HW + pxs[k]) = pv[k];
+          pxs[k] = -1;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < LPL; k++) {
+      c[k] = SGM_INF;
+      if (d0 + k < D) {
+        const float* r = vp + (long)k * HW;
+        if (VEC) {
+          const int j = (x + ph[k]) & 3, xs = x - j;
+          c[k] = (xs >= 0 && xs + 3 < n) ? pick(cv[k], j) : r[x];
+        } else {
+          c[k] = r[x * sstride];
+        }
+      }
+    }
+    if (i == 0) {
+#pragma unroll
+      for (int k = 0; k < LPL; k++) L[k] = c[k];
+    } else {
+      float m = L[0];
+#pragma unroll
+      for (int k = 1; k < LPL; k++) m = fminf(m, L[k]);
+      m = wave_min(m);
+      float up = __shfl_up(L[LPL - 1], 1), dn = __shfl_down(L[0], 1);
+      if (lane == 0) up = SGM_INF;
+      if (lane == 63) dn = SGM_INF;
+      if constexpr (MW) {
+        __shared__ float ex[2][16][3];  // {minimum, first level, last level} of each wave
+        const int par = i & 1, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+        if (lane == 0) {
+          ex[par][w][0] = m;
+          ex[par][w][1] = L[0];
+        }
+        if (lane == 63) ex[par][w][2] = L[LPL - 1];
+        // a wave writes buffer par again two steps on, past the next barrier: every wave has read this one by then
+        __syncthreads();
+        m = ex[par][0][0];
+        for (int v = 1; v < nw; v++) m = fminf(m, ex[par][v][0]);
+        if (lane == 0 && w > 0) up = ex[par][w - 1][2];
+        if (lane == 63 && w + 1 < nw) dn = ex[par][w + 1][1];
+      }
+      sgm_step<LPL>(L, c, up, dn, m, P1, P2);
+    }
+#pragma unroll
+    for (int k = 0; k < LPL; k++) {
+      if (d0 + k < D) {
+        float* r = ap + (long)k * HW;
+        if (VEC) {
+          const int j = (x + ph[k]) & 3, xs = x - j;
+          if (xs >= 0 && xs + 3 < n) {
+            put(av[k], j, acc ? pick(av[k], j) + L[k] : L[k]);
+            if (j == js) {  // the piece is complete: stored at the next step, after that step's loads
+              pv[k] = av[k];
+              pxs[k] = xs;
+            }
+          } else {
+            r[x] = acc ? r[x] + L[k] : L[k];
+          }
+        } else {
+          const int o = x * sstride;
+          r[o] = acc ? r[o] + L[k] : L[k];
+        }
+      }
+    }
+  }
+  if (VEC) {
+#pragma unroll
+    for (int k = 0; k < LPL; k++)
+      if (pxs[k] >= 0) *(float4*)(ap + (long)k * HW + pxs[k]) = pv[k];
+  }
+}
+
+constexpr int LPW = plan::kSgmColumnsLpw;
+
+// NT: the workgroup's thread limit (512 up to 8 waves: 128 levels)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_sgm_columns(const float* __restrict__ vol, float* __restrict__ agg, int D, int W,
+                                                    int H, int rev, int acc, float P1, float P2) {
+  __shared__ float ex[2][NT / 64][3][64];  // per wave and column: {chunk minimum, first level, last level}
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int x = blockIdx.x * 64 + lane;
+  const bool in = x < W;  // a column past the image: +inf (NaN from the second row on), read and stored nowhere
+  const long HW = (long)W * H;
+  const int dw = w * LPW;
+  const float* vw = vol + (long)dw * HW;
+  float* aw = agg + (long)dw * HW;
+  float L[LPW], c[LPW], a[LPW];
+  const auto load = [&](const float* pl, int y, float(&cc)[LPW], float pad) {
+    const int off = y * W + x;
+#pragma unroll
+    for (int k = 0; k < LPW; k++) {
+      cc[k] = pad;
+      if (in && dw + k < D) cc[k] = pl[(long)k * HW + off];
+    }
+  };
+  const int dy = rev ? -1 : 1;
+  int y = rev ? H - 1 : 0;
+  load(vw, y, c, SGM_INF);
+  if (acc) load(aw, y, a, 0.0f);
+  for (int i = 0; i < H; i++, y += dy) {
+    // the next row's costs and agg are on their way while the waves meet, and are issued before this row's
+    // stores: memory operations retire in order, so a load issued behind a store waits for the store as well
+    float cn[LPW], an[LPW];
+    if (i + 1 < H) {
+      load(vw, y + dy, cn, SGM_INF);
+      if (acc) load(aw, y + dy, an, 0.0f);
+    }
+    if (i == 0) {
+#pragma unroll
+      for (int k = 0; k < LPW; k++) L[k] = c[k];
+    } else {
+      const int par = i & 1;
+      float m = L[0];
+#pragma unroll
+      for (int k = 1; k < LPW; k++) m = fminf(m, L[k]);
+      ex[par][w][0][lane] = m;
+      ex[par][w][1][lane] = L[0];
+      ex[par][w][2][lane] = L[LPW - 1];
+      // a wave writes buffer par again two rows on, past the next barrier: every wave has read this one by then
+      __syncthreads();
+      m = ex[par][0][0][lane];
+      for (int v = 1; v < nw; v++) m = fminf(m, ex[par][v][0][lane]);
+      const float up = w > 0 ? ex[par][w - 1][2][lane] : SGM_INF;
+      const float dn = w + 1 < nw ? ex[par][w + 1][1][lane] : SGM_INF;
+      sgm_step<LPW>(L, c, up, dn, m, P1, P2);
+    }
+    const int off = y * W + x;
+#pragma unroll
+    for (int k = 0; k < LPW; k++)
+      if (in && dw + k < D) aw[(long)k * HW + off] = acc ? a[k] + L[k] : L[k];
+    if (i + 1 < H) {
+#pragma unroll
+      for (int k = 0; k < LPW; k++) {
+        c[k] = cn[k];
+        if (acc) a[k] = an[k];
+      }
+    }
+  }
+}
+
+template <bool VEC, bool MW>
+void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const float* vol, float* agg, int D, long HW, int acc,
+                  float P1, float P2) {
+#define SGM_LANES(LPL)                                                                                            \
+  hipLaunchKernelGGL((k_sgm_lanes<LPL, VEC, MW>), dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, HW, p.n, p.sstride, \
+                     p.lstride, (int)p.rev, acc, P1, P2)
+  if constexpr (MW) {
+    SGM_LANES(16);
+  } else {
+    switch (p.lpl) {
+      case 1: SGM_LANES(1); break;
+      case 2: SGM_LANES(2); break;
+      case 4: SGM_LANES(4); break;
+      case 8: SGM_LANES(8); break;
+      default: SGM_LANES(16); break;
+    }
+  }
+#undef SGM_LANES
+}
+
+}  // namespace
+
+int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
+  const long HW = (long)W * H;
+  int acc = 0;  // the first set path stores, the later ones add
+  for (int path = 0; path < 4; path++) {
+    if (!((paths >> path) & 1)) continue;
+    const plan::SgmPlan p = plan::plan_sgm(W, H, D, path);
+    if (p.err) return arg_fail(p.err);
+    if (p.form == plan::kSgmColumns) {
+      if (p.block <= 512)
+        hipLaunchKernelGGL(k_sgm_columns<512>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, (int)p.rev, acc, P1,
+                           P2);
+      else
+        hipLaunchKernelGGL(k_sgm_columns<1024>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, (int)p.rev, acc,
+                           P1, P2);
+    } else if (p.waves > 1) {
+      launch_lanes<false, true>(s, p, vol, agg, D, HW, acc, P1, P2);
+    } else if (p.vec && (((uintptr_t)vol ^ (uintptr_t)agg) & 15) == 0) {
+      launch_lanes<true, false>(s, p, vol, agg, D, HW, acc, P1, P2);
+    } else {
+      launch_lanes<false, false>(s, p, vol, agg, D, HW, acc, P1, P2);
+    }
+    MVS_LAUNCH_CHECK("k_sgm");
+    acc = 1;
+  }
+  return 0;
+}
+
+}  // namespace mvs

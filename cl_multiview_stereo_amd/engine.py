@@ -323,6 +323,20 @@ class Engine:
         _lib.check(self.L.mvs_wta_sub_d(self.ctx, W, H, D, _ptr(vol), _ptr(levels), _ptr(out)), "mvs_wta_sub_d")
         return out
 
+    def sgm(self, vol, P1: float = 0.1, P2: float = 0.8, paths: int = 15, out=None):
+        """Semi-global aggregation of a volume [D, H, W] (include/mvs.h at mvs_sgm_d): the path
+        costs of the paths in the mask (1 left->right, 2 right->left, 4 top->bottom, 8 bottom->top)
+        summed in bit order into out [D, H, W], which must not be vol.  wta on the result gives the
+        aggregated disparity and confidence."""
+        D, H, W = vol.shape
+        out = self.empty((D, H, W), torch.float32) if out is None else out
+        if tuple(out.shape) != (D, H, W) or vol.dtype != torch.float32 or out.dtype != torch.float32:
+            raise ValueError("sgm: vol and out must be float32 [D, H, W]")
+        self._stream()
+        _lib.check(self.L.mvs_sgm_d(self.ctx, W, H, D, _ptr(vol), C.c_float(P1), C.c_float(P2), int(paths),
+                                    _ptr(out)), "mvs_sgm_d")
+        return out
+
     def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):
         """The same for reference views [z0, z1) without a volume: disp [z1 - z0, H, W] is what
         ncc_wta_range wrote; the three costs are recomputed from the window planes (bit-identical

@@ -64,18 +64,30 @@ class PixelSweep:
     volume in HBM, same disp/conf bits).  cost="sad": the reference sweep at
     S=1 grid semantics (parity).  subpixel=True (NCC only): run() also leaves
     the sub-level disparity (the parabola fit of include/mvs.h) of the views
-    it swept in self.disp_sub; disp and conf are unchanged."""
+    it swept in self.disp_sub; disp and conf are unchanged.  sgm=True (NCC
+    only): run() also leaves the winner and confidence of the semi-globally
+    aggregated volume (mvs_sgm_d, all four paths, penalties sgm_p1 <= sgm_p2)
+    in self.disp_agg and self.conf_agg [z1 - z0, H, W]: per view ncc_volume ->
+    sgm -> wta, through one more [D, H, W] buffer; with fused=True the volume
+    is computed for this alone.  disp, conf and disp_sub are unchanged."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
-                 fused: bool = False, subpixel: bool = False):
+                 fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
+                 sgm_p2: float = 0.8):
         if subpixel and cost != "ncc":
             raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
+        if sgm and cost != "ncc":
+            raise ValueError("sgm=True needs cost=\"ncc\": the aggregation runs on the NCC cost volume")
         self.e, self.cam, self.W, self.H = engine, cam, W, H
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
+        self.sgm, self.sgm_p1, self.sgm_p2 = sgm, sgm_p1, sgm_p2
         self.disp_sub = None
-        self.vol = None
-        if cost == "ncc" and not fused:
+        self.disp_agg = self.conf_agg = None
+        self.vol = self.agg = None
+        if cost == "ncc" and (sgm or not fused):
             self.vol = engine.empty((cam.D, H, W), torch.float32)
+        if sgm:
+            self.agg = engine.empty((cam.D, H, W), torch.float32)
         self.levels = engine.levels_dev(cam)
 
     def run(self, lab, l8, z0: int, z1: int, disp_out=None, conf_out=None, views=None):
@@ -93,10 +105,17 @@ class PixelSweep:
         else:
             V, H, W = l8.shape
             box = self.e.box_stats_views(l8, self.K, views, self.e.empty((2, V, H + (H & 1), W, 2), torch.int32))
+        if self.sgm:
+            self.disp_agg = self.e.empty((n, self.H, self.W), torch.float32)
+            self.conf_agg = self.e.empty((n, self.H, self.W), torch.float32)
         if self.fused:  # every reference view of the call, runs of views per launch
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
             if self.subpixel:  # the post-pass over the whole range, one call
                 self.disp_sub = self.e.ncc_sub_range(l8, box, self.cam, z0, z1, self.K, disp=disp)
+            if self.sgm:  # the volume the fused sweep never stores, for the aggregation alone
+                for i, z in enumerate(range(z0, z1)):
+                    self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
+                    self._aggregate(i)
             return disp, conf
         if self.subpixel:
             self.disp_sub = self.e.empty((n, self.H, self.W), torch.float32)
@@ -105,7 +124,14 @@ class PixelSweep:
             self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
             if self.subpixel:
                 self.e.wta_sub(self.vol, self.levels, out=self.disp_sub[i])
+            if self.sgm:
+                self._aggregate(i)
         return disp, conf
+
+    def _aggregate(self, i: int):
+        """self.vol -> sgm -> wta into view i of disp_agg / conf_agg."""
+        self.e.sgm(self.vol, self.sgm_p1, self.sgm_p2, out=self.agg)
+        self.e.wta(self.agg, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
 
 class DepthRefinement:
@@ -137,6 +163,8 @@ class StepOutput:
     disp: torch.Tensor | None = None
     conf: torch.Tensor | None = None
     disp_sub: torch.Tensor | None = None  # sub-level disparity (Pipeline(subpixel=True)), else None
+    disp_agg: torch.Tensor | None = None  # winner of the semi-globally aggregated volume (Pipeline(sgm=True)), else None
+    conf_agg: torch.Tensor | None = None  # its confidence
     disp_refined: torch.Tensor | None = None
     disp_filtered: torch.Tensor | None = None
 
@@ -160,7 +188,7 @@ class Pipeline:
     def __init__(self, engine: Engine, settings: params.Settings, W: int, H: int,
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
                  refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
-                 subpixel: bool = False):
+                 subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8):
         self.e, self.st, self.W, self.H = engine, settings, W, H
         vs = view_subset if view_subset is not None else params.neighbour_lists(
             settings.array_width, settings.array_height, settings.neib_hor, settings.neib_ver)
@@ -171,7 +199,10 @@ class Pipeline:
         self.photo = PhotoConsistency(engine, self.cam, settings.spixl_size)
         if subpixel and pixel_cost != "ncc":
             raise ValueError("subpixel=True needs pixel_cost=\"ncc\"")
-        self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel)
+        if sgm and pixel_cost != "ncc":
+            raise ValueError("sgm=True needs pixel_cost=\"ncc\"")
+        self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
+                                 sgm_p2)
                       if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None
@@ -209,6 +240,8 @@ class Pipeline:
             out = StepOutput(lab, spixl, labels, rep, disp, conf)
         if self.pixel is not None and self.pixel.subpixel:
             out.disp_sub = self.pixel.disp_sub
+        if self.pixel is not None and self.pixel.sgm:
+            out.disp_agg, out.conf_agg = self.pixel.disp_agg, self.pixel.conf_agg
         if self.refiner is not None:
             r = self.refiner.do_refinement(spixl, labels, rep, self.st)
             out.disp_refined = r["disp"]

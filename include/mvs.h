@@ -205,6 +205,33 @@ int mvs_wta_sub_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, const flo
  * range); a disparity that matches no level is copied.  l8 is validated only. */
 int mvs_ncc_sub_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a,
                         int K, int z0, int z1, const float* disp, float* disp_sub);
+/* Semi-global aggregation of a cost volume along the four axis-aligned paths
+ * (0.9.1).  vol, agg [D][H][W]; vol holds no NaN and no -0.0 (mvs_ncc_volume_d's
+ * output holds neither); P1, P2 finite with 0 <= P1 <= P2.  All arithmetic is
+ * float32, every operation rounded; there is no multiply, so nothing fuses.
+ * A path r visits the pixels of one image row or column in order; q is the
+ * pixel before p on it:
+ *   first pixel of the path:  L_r(p, d) = vol[d][p]
+ *   else:  m = min over k of L_r(q, k)
+ *          t = min( L_r(q, d),
+ *                   L_r(q, d-1) + P1   (d > 0 only),
+ *                   L_r(q, d+1) + P1   (d < D-1 only),
+ *                   m + P2 )
+ *          L_r(p, d) = (vol[d][p] + t) - m
+ * d-1 and d+1 are index neighbours: the spacing of the levels plays no part.
+ * paths is a mask: bit 0 left->right (+x in each row), bit 1 right->left,
+ * bit 2 top->bottom (+y in each column), bit 3 bottom->top.
+ *   agg = ((L_b0 + L_b1) + L_b2) + L_b3
+ * over the set bits, in bit order, rounded after each add; the first set path
+ * is stored as it is (whatever agg held before is overwritten).
+ * mvs_wta_d on agg gives the aggregated disparity and confidence.
+ * mvs_wta_sub_d on agg is NOT defined: its ok rule reads a cost of 2 as "no
+ * measurement", which does not carry over to sums; take the sub-level
+ * disparity from the raw volume.
+ * MVS_E_ARG: a null pointer, bad W or H, D < 1 or D > 16384, paths outside
+ * 1..15, a penalty that is not finite, negative, or P1 > P2, agg == vol (the
+ * two must not overlap at all).  Nothing is allocated. */
+int mvs_sgm_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg);
 /* Tuning / test hook: the NCC sweep variant this context tries first (0 =
  * automatic): waves per workgroup 4|8, levels per wave 1|2|4,
  * minimum LDS band width 64|80|96|128|192|256 columns, general_rows 1 = the kernel
