@@ -5,9 +5,9 @@
 // form, grids, the re-layout slot table, the SAD step records, LDS bytes) as
 // plain C++ with no HIP header and no mvs_ctx, so it builds with g++ and runs
 // without a GPU (tests/host/launch_plan_check.cpp prints its decisions).
-// slic.hip, sweep.hip and refine.hip map a plan to a kernel instantiation and
-// launch it.  The structs and constants below that a kernel reads too are
-// defined here once.
+// slic.hip, sweep.hip, sad.hip and refine.hip map a plan to a kernel
+// instantiation and launch it.  The structs and constants below that a kernel
+// reads too are defined here once.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -28,7 +28,14 @@ constexpr int kAssignTW = 64, kAssignTH = 16;  // k_assign's pixel tile (AS_TW, 
 // ---- shared with k_sweep_spixl_ring (sweep.hip) ----------------------------
 constexpr int kSwU = 336;  // C5 (S = 40, |dx| <= 4): 78 + 2 + 252 = 332
 
-// ---- shared with k_sad_band / k_sweep_pixel_sad (sweep.hip) ----------------
+// ---- shared with k_sweep_spixl* (sweep.hip) and k_sweep_pixel_sad (sad.hip) --
+struct SweepArgs {
+  int V, W, H, mw, mh, D, aw, z;
+  float bl;
+};
+constexpr float SB_INIT = 1000000.0f;  // initial_depth_estimation_v2's initial cost: every SAD sweep form's minima start here
+
+// ---- shared with k_sad_band / k_sweep_pixel_sad (sad.hip) ------------------
 constexpr int SB_TW = 60;   // output columns per tile
 constexpr int SB_NBLK = 2;  // 64-column blocks per band row (band columns <= 128)
 struct SadArgs {

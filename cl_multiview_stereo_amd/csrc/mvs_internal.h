@@ -124,7 +124,7 @@ int launch_ncc_refs(mvs_ctx* ctx, int V, int W, int H, const int32_t* box, const
                     const float* levels_dev, float* disp, float* conf);
 int launch_wta(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp,
                float* conf);
-// sub-level disparity (ncc_sub.hip): over a volume; for reference views [z0, z1) from the window planes
+// sub-level disparity: over a volume (wta.hip); for reference views [z0, z1) from the window planes (ncc_sub.hip)
 int launch_wta_sub(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp_sub);
 int launch_ncc_sub(hipStream_t s, int V, int W, int H, const int32_t* box, const float* levels_dev, int D,
                    const int* vs_dev, const int* sn_dev, int aw, float bl, int K, int z0, int z1, const float* disp,

@@ -224,8 +224,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     u32x4* nst = npk + a.pk_pairs * BW;
     if (a.plane32) {
       const int pb = 16 * W;  // bytes per pair row
-      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(pk + vo), 0, pb * Hp2, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(stats + vo), 0, pb * Hp2, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rp = buf_rsrc(pk + vo, pb * Hp2);
+      const __amdgpu_buffer_rsrc_t rs = buf_rsrc(stats + vo, pb * Hp2);
       for (int cb = 0; cb < nblk; cb++) {
         const int c0 = min(cb * 64, span);
         const int voff = 16 * min(max(x0 - e.txmax + c0 + lane, 0), W - 1);
@@ -328,8 +328,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (dl >= a.D) break;
       // buffer stores: the level plane as a buffer resource (scalar), the lane's
       // byte offset fixed for the tile, the row offset scalar -- no address VALU
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc(vol + (long)dl * P, 0, (int)(P * 4), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = buf_rsrc(vol + (long)dl * P, (int)(P * 4));
       const int off0 = (y0 * W + x) * 4;
       // cost pairs: m*s_r as one v_pk_mul_f32, 1 - c as one v_pk_add_f32
       float cst[TH];

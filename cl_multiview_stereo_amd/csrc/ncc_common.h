@@ -1,12 +1,13 @@
-// Shared by the NCC sweep kernels (ncc.hip: scalar forms and the window
-// planes; ncc_mfma.hip: the matrix-core form): row-pair plane indexing, the
-// LDS-DMA and the exact min / max / med3 helpers.  The launch arguments and
-// every host-side decision are ncc_plan.h's.
+// Shared by the NCC kernels (ncc.hip: scalar forms and the window planes; ncc_mfma.hip: the matrix-core
+// form; ncc_sub.hip and wta.hip: the sub-level fit): row-pair plane indexing, the band reads, the exact
+// min / max / med3 helpers, the winner-take-all's initial cost and the fit.  Wave-level helpers: wave.h;
+// the launch arguments and every host-side decision: ncc_plan.h.
 #pragma once
 #include <cstdint>
 #include <vector>
 #include "mvs_internal.h"
 #include "ncc_plan.h"  // NccArgs, the parity modes, NccLaunch
+#include "wave.h"
 
 namespace mvs {
 namespace ncc {
@@ -30,13 +31,6 @@ struct alignas(128) NccRec {
   int pad[12];
 };
 static_assert(sizeof(NccRec) == 4 * kRecWords, "the planner writes 32-word records");
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-// 16-byte LDS-DMA: lane l's 16 bytes land at dst + 16*l (dst wave-uniform)
-__device__ __forceinline__ void glds_b128(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)dst, 16, 0, 0);
-}
 
 // v_max_f32 (IEEE maxNum: a quiet-NaN operand is dropped).  Inline asm so the
 // compiler does not re-canonicalise the loop-carried accumulators every pass.
@@ -97,10 +91,17 @@ struct WtaOut {
   float* disp;          // [H][W]
   float* conf;          // [H][W] or null
 };
-constexpr float kWtaInit = 1000000.0f;  // k_wta's Top4 initial cost (sweep.hip)
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// the initial cost of the volume pass (k_wta's Top4, wta.hip) and of both fused folds
+constexpr float kWtaInit = 1000000.0f;
+// the sub-level fit (ncc_sub.hip's header); lm, lb, lp = levels[b-1], levels[b], levels[b+1]
+__device__ __forceinline__ float parabola(float cm, float c0, float cp, float lm, float lb, float lp) {
+  if (!(cm < 2.0f && cp < 2.0f)) return lb;
+  const float den = (cm - c0) + (cp - c0);
+  const float off = (0.5f * (cm - cp)) / den;
+  const float step = off < 0.0f ? lb - lm : lp - lb;
+  const float t = off * step;
+  return lb + t;
+}
 
 // N consecutive band rows starting at band row r0 of a row-pair band (pair
 // row stride BW, one column): ds_read_b128 per pair; an odd start takes the
@@ -127,9 +128,6 @@ __device__ __forceinline__ void read_rows(const u32x4* col, int r0, u32x2 (&v)[N
   }
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // The N/2 stats row pairs (o, o+1), o even, of a band column starting at band
 // row r0: {a(o), a(o+1), b(o), b(o+1)}.  An odd start joins the second row of
 // one stored pair with the first row of the next.
@@ -154,58 +152,13 @@ __device__ __forceinline__ void read_stat_pairs(const u32x4* col, int r0, f32x4 
   }
 }
 
-// v_dot4_i32_i8 is the VOP3P form (separate destination): a prefix-sum chain
-// keeps every partial sum without the accumulator copies the VOP2 v_dot4c
-// form forces.  The Makefile builds this file with the dot6 feature (v_dot4c)
-// off, so the compiler selects the VOP3P form and still tracks its hazards.
-// s_waitcnt vmcnt(min(n, 6)) (n >= 0; a count above 6 waits for 6: still
-// correct for a caller that needs at most n outstanding, only earlier)
-__device__ __forceinline__ void wait_vm_le(int n) {
-  switch (n) {
-    case 0: __builtin_amdgcn_s_waitcnt(0x0f70); break;
-    case 1: __builtin_amdgcn_s_waitcnt(0x0f71); break;
-    case 2: __builtin_amdgcn_s_waitcnt(0x0f72); break;
-    case 3: __builtin_amdgcn_s_waitcnt(0x0f73); break;
-    case 4: __builtin_amdgcn_s_waitcnt(0x0f74); break;
-    case 5: __builtin_amdgcn_s_waitcnt(0x0f75); break;
-    default: __builtin_amdgcn_s_waitcnt(0x0f76); break;
-  }
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n in [0, 6] (n > 6: vmcnt(6)), then
-// s_barrier -- the selection inside one asm block, so the compiler sees no
-// branch (a C-level switch split the step and spilled the fold's registers)
-__device__ __forceinline__ void wait_vm_barrier(int n) {
-  asm volatile(
-      "s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 10f\n\t"
-      "s_cmp_eq_u32 %0, 1\n\ts_cbranch_scc1 11f\n\t"
-      "s_cmp_eq_u32 %0, 2\n\ts_cbranch_scc1 12f\n\t"
-      "s_cmp_eq_u32 %0, 3\n\ts_cbranch_scc1 13f\n\t"
-      "s_cmp_eq_u32 %0, 4\n\ts_cbranch_scc1 14f\n\t"
-      "s_cmp_eq_u32 %0, 5\n\ts_cbranch_scc1 15f\n\t"
-      "s_waitcnt vmcnt(6)\n\ts_branch 19f\n"
-      "10:\n\ts_waitcnt vmcnt(0)\n\ts_branch 19f\n"
-      "11:\n\ts_waitcnt vmcnt(1)\n\ts_branch 19f\n"
-      "12:\n\ts_waitcnt vmcnt(2)\n\ts_branch 19f\n"
-      "13:\n\ts_waitcnt vmcnt(3)\n\ts_branch 19f\n"
-      "14:\n\ts_waitcnt vmcnt(4)\n\ts_branch 19f\n"
-      "15:\n\ts_waitcnt vmcnt(5)\n"
-      "19:\n\ts_barrier"
-      :
-      : "s"(n)
-      : "memory", "scc");
-}
-
-// the lane id, recomputed where it is used (volatile: never hoisted, so it is
-// never a long-lived value the register allocator would spill)
-__device__ __forceinline__ int lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
 constexpr int kMagicI = 0x4B400000;  // the bits of 12582912.0f = 1.5 * 2^23
 constexpr float kMagicF = 12582912.0f;
+// v_dot4_i32_i8 is the VOP3P form (separate destination): a prefix-sum chain
+// keeps every partial sum without the accumulator copies the VOP2 v_dot4c
+// form forces.  The Makefile builds the ncc*.hip files with the dot6 feature
+// (v_dot4c) off, so the compiler selects the VOP3P form and still tracks its
+// hazards.
 __device__ __forceinline__ int dot4(unsigned a, unsigned b, int c) {
   return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
 }

@@ -65,7 +65,6 @@ struct alignas(128) NccMRec {
   int pad[8];
 };
 static_assert(sizeof(NccMRec) == 4 * kRecWords, "one 128-B record per (chunk, neighbour)");
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // A tile is 64 columns x 8 rows: a wave owns 8 columns x 8 rows = 4 pixel
 // blocks (K = 5: 4 x 4 pixels, one MFMA per level block; K = 7: 2 columns x
@@ -151,10 +150,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     u32x4* nst = nbase + b * nbuf + a.pk_pairs * BWP + ((K == 7 && wave >= 2) ? ((e.shp << 16) >> 24) : 0);
     // the wave's roles (pk row w < bhp, stats row w < shp) decided once per step, not per piece
     if (wave < shp) {
-      const __amdgpu_buffer_rsrc_t rp =
-          __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)pk + vo + 8 * pk_row), 0, 16 * W, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)stats + vo + 8 * st_row), 0, 16 * W, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rp = buf_rsrc((const char*)pk + vo + 8 * pk_row, 16 * W);
+      const __amdgpu_buffer_rsrc_t rs = buf_rsrc((const char*)stats + vo + 8 * st_row, 16 * W);
       for (int cb = 0; cb < nblk; cb++) {
         const int c0 = min(cb * 64, span);
         const int voff = 16 * min(max(lane_x - e.tx + c0, 0), W - 1);
@@ -162,8 +159,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(nst + wave * BWP + c0), 16, voff, 0, 0, 0);
       }
     } else if (wave < bhp) {
-      const __amdgpu_buffer_rsrc_t rp =
-          __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)pk + vo + 8 * pk_row), 0, 16 * W, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rp = buf_rsrc((const char*)pk + vo + 8 * pk_row, 16 * W);
       for (int cb = 0; cb < nblk; cb++) {
         const int c0 = min(cb * 64, span);
         const int voff = 16 * min(max(lane_x - e.tx + c0, 0), W - 1);
@@ -221,8 +217,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
   // read through one buffer descriptor based there: a row is a scalar offset,
   // a column a 32-bit lane offset, no per-lane 64-bit address arithmetic.
   const int zp0 = min(max((y0 >> 1) - (K == 5 ? 1 : 2), 0), Hp2 - 1);
-  const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((const char*)pk + 8 * (zo + 2L * W * zp0)), 0, 16 * W * min(Hp2 - zp0, 8), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rz = buf_rsrc((const char*)pk + 8 * (zo + 2L * W * zp0), 16 * W * min(Hp2 - zp0, 8));
   // -Sr' and s_r of the tile's 64 x TH pixels (lane = column), as k_ncc_volume:
   // wave w takes rows w, w + 8, ... (one correctly rounded sqrt + divide per
   // row and lane, spread over the waves instead of TH of them on wave 0)

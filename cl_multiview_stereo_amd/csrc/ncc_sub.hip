@@ -12,7 +12,8 @@
 //   step = off < 0 ? levels[b] - levels[b-1] : levels[b+1] - levels[b]
 //   disp_sub = ok ? levels[b] + off * step : levels[b]
 //
-// k_wta_sub streams a materialised volume (the two-pass path).  k_ncc_sub is
+// k_wta_sub (wta.hip) streams a materialised volume (the two-pass path); the
+// fit itself is ncc_common.h's parabola, shared by both.  k_ncc_sub is
 // the post-pass of the fused sweep, which keeps no volume: it recovers b from
 // the integer-level disparity the sweep wrote (levels strictly increasing: a
 // binary search by value) and recomputes the three costs from the window
@@ -42,45 +43,7 @@ namespace mvs {
 namespace {
 using namespace ncc;
 
-// the fit; lm, lb, lp = levels[b-1], levels[b], levels[b+1]
-__device__ __forceinline__ float parabola(float cm, float c0, float cp, float lm, float lb, float lp) {
-  if (!(cm < 2.0f && cp < 2.0f)) return lb;
-  const float den = (cm - c0) + (cp - c0);
-  const float off = (0.5f * (cm - cp)) / den;
-  const float step = off < 0.0f ? lb - lm : lp - lb;
-  const float t = off * step;
-  return lb + t;
-}
-
-__global__ __launch_bounds__(256) void k_wta_sub(const float* __restrict__ vol, const float* __restrict__ levels,
-                                                 long P, int D, float* __restrict__ out) {
-  const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  const float* col = vol + p;
-  float best = __builtin_nontemporal_load(col);
-  int b = 0;
-#pragma unroll 8
-  for (int dl = 1; dl < D; dl++) {
-    const float c = __builtin_nontemporal_load(col + (long)dl * P);
-    if (c < best) {
-      best = c;
-      b = dl;
-    }
-  }
-  float r = levels[b];
-  if (b > 0 && b < D - 1)
-    r = parabola(col[(long)(b - 1) * P], best, col[(long)(b + 1) * P], levels[b - 1], r, levels[b + 1]);
-  out[p] = r;
-}
-
 constexpr int kSubLdsLevels = 1024;  // levels kept in LDS by k_ncc_sub (4 KB); more are searched in global memory
-
-// roundf(v) as truncf(v + copysignf(0.49999997f, v)): equal for every non-NaN
-// float (refine.hip's round_ha; checked over all 2^32 encodings by
-// tests/test_oracle_cpu.py test_round_half_away_identity)
-__device__ __forceinline__ float round_ha(float v) {
-  return truncf(v + copysignf(__int_as_float(0x3effffff), v));
-}
 
 // Image rows r0 .. r0 + K - 1 (all inside the image) of column xc of one
 // view's packed plane: the (K+1)/2 row pairs holding them as 16-byte reads at
@@ -247,13 +210,6 @@ __global__ __launch_bounds__(256) void k_ncc_sub(const uint2* __restrict__ stats
 }
 
 }  // namespace
-
-int launch_wta_sub(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp_sub) {
-  const long P = (long)W * H;
-  hipLaunchKernelGGL(k_wta_sub, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, vol, levels, P, D, disp_sub);
-  MVS_LAUNCH_CHECK("k_wta_sub");
-  return 0;
-}
 
 int launch_ncc_sub(hipStream_t s, int V, int W, int H, const int32_t* box, const float* levels_dev, int D,
                    const int* vs_dev, const int* sn_dev, int aw, float bl, int K, int z0, int z1, const float* disp,

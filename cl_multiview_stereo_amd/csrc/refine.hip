@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "mvs_internal.h"
+#include "wave.h"
 
 namespace mvs {
 namespace {
@@ -26,14 +27,7 @@ struct RArgs {
 
 __device__ __forceinline__ float expf_neg_sq(float diff, float k) { return mvs_expf(((-diff) * diff) * k); }
 
-// roundf(v) as truncf(v + copysignf(0.49999997f, v)): equal for every non-NaN
-// float (checked exhaustively over all 2^32 encodings, tests/test_oracle_cpu.py
-// test_round_half_away_identity); 3 VALU instead of ~6.  NaN stays NaN.
-__device__ __forceinline__ float round_ha(float v) {
-  return truncf(v + copysignf(__int_as_float(0x3effffff), v));
-}
-
-// c - round_ha(v) as an int, for integral c: (int)(fc - round_ha(v)) without
+// c - round_ha(v) (wave.h) as an int, for integral c: (int)(fc - round_ha(v)) without
 // the float subtract and truncate.  Equal wherever either lands in an image
 // ([0, 2^24)): round_ha(v) is then integral and exact, and outside it both are
 // out of range (the convert saturates; NaN converts to 0 either way, and a NaN
@@ -817,9 +811,6 @@ __global__ void k_spixl_to_image(const float* __restrict__ spixl, const LT* __re
   disp[P * z + (long)W * y + x] = v / t[5];
 }
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-
 // The same map, 4 consecutive pixels per thread (W % 4 == 0): one 16-B (u32
 // labels) or 8-B (u16) label load and one 16-B store per thread, the record gathers as buffer loads
 // with 32-bit offsets inside view z's records (a label is the superpixel
@@ -833,8 +824,8 @@ __global__ __launch_bounds__(256) void k_spixl_to_image4(const float* __restrict
   const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x), y = blockIdx.y, z = blockIdx.z;
   if (x >= W) return;
   const long M = (long)mw * mh, P = (long)W * H, p = P * z + (long)W * y + x;
-  const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc((void*)(spixl + 8 * M * z), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc((void*)(st + 6 * M * z), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsp = buf_rsrc(spixl + 8 * M * z, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rst = buf_rsrc(st + 6 * M * z, 0x7fffffff);
   unsigned ids[4];
   if (sizeof(LT) == 4) {
     const uint4 id4 = *(const uint4*)(labels + p);
@@ -911,7 +902,7 @@ __global__ __launch_bounds__(256) void k_proj_inv(const float* __restrict__ full
       const int xp = (int)(xf - round_ha(md * (float)(crx - cx)));
       const int yp = (int)(yf - round_ha((bl * md) * (float)(cry - cy)));
       const bool in = (unsigned)xp < (unsigned)W && (unsigned)yp < (unsigned)H;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 0x7fffffff, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = buf_rsrc(vb, 0x7fffffff);
       const int off = in ? (int)((unsigned)yp * (unsigned)W + (unsigned)xp) * 4 : 0x7fffffff;
       const float cd = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
       if (in && md < cd) md = cd;
@@ -984,7 +975,7 @@ __global__ __launch_bounds__(256) void k_remove_incons_sel(const float* __restri
   const long P = (long)W * H, p = (long)y * W + x;
   const unsigned P4 = (unsigned)(P * 4);
   const float xf = (float)x, yf = (float)y;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)full, 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(full, 0x7fffffff);
   float pv[MAXV];
   unsigned long long live = 0ull;  // candidates not yet tried: d != 0
 #pragma unroll
@@ -1290,7 +1281,7 @@ __global__ __launch_bounds__(64 * RG) void k_remove_incons_q(const float* __rest
   const int r = z0 + RG * fg.g + wave;
   if (r >= z1 || !xin) return;  // after the barriers
   const unsigned P4 = (unsigned)(P * 4);  // the launcher checks V * P * 4 < 2^31
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)full, 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(full, 0x7fffffff);
   const int nd = S.nd[lane];
   int best = nd;  // smallest candidate index found stable (nd: none yet)
   int nxt = 0;    // next candidate to hand to a slot
@@ -1394,6 +1385,17 @@ __global__ __launch_bounds__(64 * RG) void k_remove_incons_q(const float* __rest
   out[P * r + p] = best < nd ? S.sv[best][lane] : 0.0f;
 }
 
+// k_remove_incons_q by plan coordinates: index 8 (NS == 2) + 4 (FB == 2) + 2 !ROWB + !RM.  (The tables of
+// launch_remove_incons name their kernels in the order the launcher has always instantiated them in, which
+// is the order the code object holds them in.)
+using FilterQKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
+                               long, int);
+using FilterPxKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
+                                long);
+template <int I>
+constexpr FilterQKernel filter_q =
+    k_remove_incons_q<kFilterRG, (I & 4) ? 2 : 4, (I & 8) ? 2 : 1, (I & 2) == 0, (I & 1) == 0>;
+
 }  // namespace
 
 int launch_flatness(hipStream_t s, int V, int mw, int mh, const float* spixl, float gamma, float* flat) {
@@ -1468,19 +1470,6 @@ int launch_proj_inv(hipStream_t s, int V, int W, int H, int aw, float bl, const 
   MVS_LAUNCH_CHECK("k_proj_inv");
   return 0;
 }
-
-namespace {
-// k_remove_incons_q by plan coordinates: index 8 (NS == 2) + 4 (FB == 2) + 2 !ROWB + !RM.  (The tables of
-// launch_remove_incons name their kernels in the order the launcher has always instantiated them in, which
-// is the order the code object holds them in.)
-using FilterQKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
-                               long, int);
-using FilterPxKernel = void (*)(const float*, const float*, int, int, int, int, float, float, int, int, float*, int,
-                                long);
-template <int I>
-constexpr FilterQKernel filter_q =
-    k_remove_incons_q<kFilterRG, (I & 4) ? 2 : 4, (I & 8) ? 2 : 1, (I & 2) == 0, (I & 1) == 0>;
-}  // namespace
 
 // remove_view_inconsistency for reference views [z0, z1): reads every proj
 // slice (all V must be filled) and the full disparity stack.  The kernel, its

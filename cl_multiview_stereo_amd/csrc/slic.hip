@@ -10,6 +10,7 @@
 // (update_cluster_center and finalize_reduction_result fused: no accum_map
 // round trip through HBM).
 #include "mvs_internal.h"
+#include "wave.h"
 
 namespace mvs {
 namespace {
@@ -372,6 +373,17 @@ __global__ __launch_bounds__(256) void k_assign(const float4* __restrict__ lab, 
 // ---- update_cluster_center + finalize_reduction_result -------------------
 // clcode.cl:533-611 (per-tile LDS tree) and 719-773 (in-order partial sum),
 // launch shape clSLIC.cpp:307-370.  One workgroup per (superpixel, view).
+// The last four strides of a wave tree, inside each 16-lane row: lane k adds lane k + i by DPP row_shl:i
+// (control 0x100 + i), i = 8, 4, 2, 1; a lane past the row's end adds 0.  T: float or uint32_t.
+template <int CTRL, typename T>
+__device__ __forceinline__ T dpp_add(T s) {
+  return s + __builtin_bit_cast(T, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), CTRL, 0xf, 0xf, true));
+}
+template <typename T>
+__device__ __forceinline__ T dpp_rows_sum(T s) {
+  return dpp_add<0x101>(dpp_add<0x102>(dpp_add<0x104>(dpp_add<0x108>(s))));
+}
+
 __device__ __forceinline__ float wave_tree(float v0, float v1, float v2, float v3) {
   // local_idx k = lane + 64*m holds v_m.  stride 128: k<128 gets k+128; stride
   // 64: k<64 gets k+64; strides 32..1 stay inside the wave, lane k adding lane
@@ -382,11 +394,7 @@ __device__ __forceinline__ float wave_tree(float v0, float v1, float v2, float v
   s = s + __uint_as_float(__builtin_amdgcn_permlane32_swap(u, u, false, false)[1]);
   u = __float_as_uint(s);
   s = s + __uint_as_float(__builtin_amdgcn_permlane16_swap(u, u, false, false)[1]);
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x108, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x104, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x102, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x101, 0xf, 0xf, true));
-  return s;
+  return dpp_rows_sum(s);
 }
 
 // The same tree shape over uint32 (integer sums: any order gives the same value).
@@ -394,11 +402,7 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v0, uint32_t v1, uint3
   uint32_t s = (v0 + v2) + (v1 + v3);
   s = s + __builtin_amdgcn_permlane32_swap(s, s, false, false)[1];
   s = s + __builtin_amdgcn_permlane16_swap(s, s, false, false)[1];
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x108, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x104, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x102, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x101, 0xf, 0xf, true);
-  return s;
+  return dpp_rows_sum(s);
 }
 
 // wave_tree for several channels at once, from their in-lane sums sX =
@@ -409,13 +413,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v0, uint32_t v1, uint3
 // D in the four 16-lane rows, so one DPP row_shl chain finishes all four.
 // Every channel's additions are wave_tree's, in its order.  Result lanes:
 // A 0, C 16, B 32, D 48 (wave_tree2s: A 0, B 32).
-__device__ __forceinline__ float dpp_rows_sum(float s) {
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x108, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x104, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x102, 0xf, 0xf, true));
-  s = s + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(s), 0x101, 0xf, 0xf, true));
-  return s;
-}
 __device__ __forceinline__ float halves_sum(float a, float b) {  // A in lanes 0-31, B in 32-63
   const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   return __uint_as_float(p[0]) + __uint_as_float(p[1]);
@@ -433,14 +430,9 @@ __device__ __forceinline__ float wave_tree2s(float sA, float sB) {
 // two integer sums (any order gives the same value): A in lane 0, B in lane 32
 __device__ __forceinline__ uint32_t wave_sum2_u32(uint32_t sA, uint32_t sB) {
   const auto p = __builtin_amdgcn_permlane32_swap(sA, sB, false, false);
-  uint32_t s = p[0] + p[1];
+  const uint32_t s = p[0] + p[1];
   const auto r = __builtin_amdgcn_permlane16_swap(s, s, false, false);
-  s = r[0] + r[1];
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x108, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x104, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x102, 0xf, 0xf, true);
-  s = s + (uint32_t)__builtin_amdgcn_mov_dpp((int)s, 0x101, 0xf, 0xf, true);
-  return s;
+  return dpp_rows_sum(r[0] + r[1]);
 }
 
 // One WAVE per superpixel (4 per workgroup): the wave walks the G window
@@ -565,7 +557,6 @@ __global__ __launch_bounds__(256) void k_update(const float4* __restrict__ lab, 
 //    additions are wave_tree's, in its order), accumulated in their result
 //    lanes (0: L, 32: a, 16: b), x / y / count as k_update's integer tree.
 // Bit-identical to k_update (the same per-tile trees, the same tile order).
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 template <int UT, typename LT>
 __global__ __launch_bounds__(256) void k_update_walk(const float4* __restrict__ lab, const LT* __restrict__ labels,
                                                      int W, int H, int S, int mw, int mh, int G, int cpl,
@@ -576,9 +567,8 @@ __global__ __launch_bounds__(256) void k_update_walk(const float4* __restrict__ 
   const int gx = sp % mw, gy = sp / mw;
   const long P = (long)W * H;
   // the launcher checks P * 16 < 2^31
-  const __amdgpu_buffer_rsrc_t rl =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(labels + z * P), 0, (int)(P * sizeof(LT)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(lab + z * P), 0, (int)(P * 16), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rl = buf_rsrc(labels + z * P, (int)(P * sizeof(LT)));
+  const __amdgpu_buffer_rsrc_t rc = buf_rsrc(lab + z * P, (int)(P * 16));
   const int lx = lane & 15, ly0 = lane >> 4, S3 = 3 * S;
   const int x0 = gx * S - S, y0 = gy * S - S;  // the window's origin
   const int loff = ly0 * W + lx;                // the lane's pixel offset in a tile (row m: + 4 m W)
@@ -814,8 +804,6 @@ __global__ __launch_bounds__(256) void k_assign_tiles(const float4* __restrict__
   }
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 
 // The same wave per tile for the reference's active 2x2 loop when S = 32 or
 // 64 (C2-C4's S = 32).  The tile's candidate cells are then the same four for
@@ -883,7 +871,7 @@ __global__ __launch_bounds__(256) void k_assign_tiles4(const float4* __restrict_
   // the tile's L, a, b as buffer loads: a pixel outside the image reads
   // zeros (an offset past the view's records), with no branch around it
   // (the launcher checks W H 16 < 2^31)
-  const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)L, 0, (int)(P * 16), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rl = buf_rsrc(L, (int)(P * 16));
   float4 c[4];
 #pragma unroll
   for (int m = 0; m < 4; m++) {
@@ -896,8 +884,7 @@ __global__ __launch_bounds__(256) void k_assign_tiles4(const float4* __restrict_
 #pragma unroll
   for (int i = 0; i < 4; i++) cid[i] = (float)(ccy[i] * mw + ccx[i]);
   // labels null (an update follows: its partials are all it reads): no records, every store dropped
-  const __amdgpu_buffer_rsrc_t rlb = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(labels ? labels + (long)z * P : nullptr), 0, labels ? (int)(P * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rlb = buf_rsrc(labels ? labels + (long)z * P : nullptr, labels ? (int)(P * 4) : 0);
   uint32_t lbl[4];
   int win[4];  // the pixel's candidate (-1: none, or outside the image)
   // the lane's column is the same for its 4 pixels: (x - cx)^2 of each
@@ -980,7 +967,7 @@ __global__ __launch_bounds__(256) void k_assign_tiles4(const float4* __restrict_
   }
   if (!part) return;
   float* out = part + (long)z * mw * mh * G * 6;
-  const __amdgpu_buffer_rsrc_t rpt = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, mw * mh * G * 24, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rpt = buf_rsrc(out, mw * mh * G * 24);
   constexpr int kOob = 0x7fffffff;
   // the candidate cells some pixel of the tile joined (a wave-uniform mask)
   unsigned pres = 0;

@@ -1,0 +1,114 @@
+// The passes over a materialised NCC cost volume [D][H][W] (ncc.hip's definition) for gfx950.
+//
+//  k_wta             winner-take-all + confidence over the materialised volume
+//                    (the HBM-streaming pass the roofline is quoted on); the fused
+//                    sweeps (ncc.hip, ncc_mfma.hip) fold the same from kWtaInit
+//  k_wta_sub         winner-take-all + the sub-level parabola fit (definition: ncc_sub.hip)
+#include "ncc_common.h"
+
+namespace mvs {
+namespace {
+using namespace ncc;
+
+// ---- winner-take-all + confidence ----------------------------------------
+// the 4 smallest (cost, level) of one pixel in lexicographic order
+struct Top4 {
+  float v0 = kWtaInit, v1 = kWtaInit, v2 = kWtaInit, v3 = kWtaInit;
+  int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
+  __device__ __forceinline__ void insert(float cc, int ci) {
+    if (cc < v3) {
+      if (cc < v2) {
+        v3 = v2; i3 = i2;
+        if (cc < v1) {
+          v2 = v1; i2 = i1;
+          if (cc < v0) { v1 = v0; i1 = i0; v0 = cc; i0 = ci; }
+          else { v1 = cc; i1 = ci; }
+        } else { v2 = cc; i2 = ci; }
+      } else { v3 = cc; i3 = ci; }
+    }
+  }
+  __device__ __forceinline__ void emit(const float* levels, float* disp, float* conf, long p) const {
+    disp[p] = i0 >= 0 ? levels[i0] : 0.0f;
+    if (conf) {
+      float c2 = kWtaInit;
+      if (i1 >= 0 && (i1 < i0 - 1 || i1 > i0 + 1)) c2 = v1;
+      else if (i2 >= 0 && (i2 < i0 - 1 || i2 > i0 + 1)) c2 = v2;
+      else if (i3 >= 0 && (i3 < i0 - 1 || i3 > i0 + 1)) c2 = v3;
+      conf[p] = (i0 < 0 || c2 == kWtaInit) ? 0.0f : c2 - v0;
+    }
+  }
+};
+
+// One lane per NP consecutive pixels (NP-wide non-temporal vector loads, so a
+// wave streams 256 NP contiguous bytes per level), UNR levels in flight.
+template <int NP, int UNR>
+__global__ __launch_bounds__(256) void k_wta(const float* __restrict__ vol, const float* __restrict__ levels, long P,
+                                             int D, float* __restrict__ disp, float* __restrict__ conf) {
+  typedef float vec __attribute__((ext_vector_type(NP)));
+  const long p = (blockIdx.x * (long)blockDim.x + threadIdx.x) * NP;
+  if (p >= P) return;
+  Top4 t[NP];
+  const vec* col = (const vec*)(vol + p);
+  const long Pv = P / NP;
+  int dl = 0;
+  for (; dl + UNR <= D; dl += UNR) {
+    vec c[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; u++) c[u] = __builtin_nontemporal_load(col + (long)(dl + u) * Pv);
+#pragma unroll
+    for (int u = 0; u < UNR; u++)
+#pragma unroll
+      for (int k = 0; k < NP; k++) t[k].insert(c[u][k], dl + u);
+  }
+  for (; dl < D; dl++) {
+    const vec c = col[(long)dl * Pv];
+#pragma unroll
+    for (int k = 0; k < NP; k++) t[k].insert(c[k], dl);
+  }
+#pragma unroll
+  for (int k = 0; k < NP; k++) t[k].emit(levels, disp, conf, p + k);
+}
+
+// ---- winner-take-all + sub-level fit (b and parabola: ncc_sub.hip's header) -
+__global__ __launch_bounds__(256) void k_wta_sub(const float* __restrict__ vol, const float* __restrict__ levels,
+                                                 long P, int D, float* __restrict__ out) {
+  const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  const float* col = vol + p;
+  float best = __builtin_nontemporal_load(col);
+  int b = 0;
+#pragma unroll 8
+  for (int dl = 1; dl < D; dl++) {
+    const float c = __builtin_nontemporal_load(col + (long)dl * P);
+    if (c < best) {
+      best = c;
+      b = dl;
+    }
+  }
+  float r = levels[b];
+  if (b > 0 && b < D - 1)
+    r = parabola(col[(long)(b - 1) * P], best, col[(long)(b + 1) * P], levels[b - 1], r, levels[b + 1]);
+  out[p] = r;
+}
+
+}  // namespace
+
+int launch_wta(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp,
+               float* conf) {
+  long P = (long)W * H;
+  // one pixel per lane, 16 levels in flight (C2: 0.185 -> 0.182 ms against 8; 32 no faster;
+  // wider per-lane vectors measured no faster)
+  hipLaunchKernelGGL((k_wta<1, 16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, vol, levels, P, D, disp,
+                     conf);
+  MVS_LAUNCH_CHECK("k_wta");
+  return 0;
+}
+
+int launch_wta_sub(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp_sub) {
+  const long P = (long)W * H;
+  hipLaunchKernelGGL(k_wta_sub, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, vol, levels, P, D, disp_sub);
+  MVS_LAUNCH_CHECK("k_wta_sub");
+  return 0;
+}
+
+}  // namespace mvs
