@@ -158,7 +158,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.9.1 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -368,16 +368,27 @@ int mvs_wta_sub_d(mvs_ctx* c, int W, int H, int D, const float* vol, const float
   return mvs::launch_wta_sub(c->stream, W, H, D, vol, levels, disp_sub);
 }
 
-int mvs_sgm_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
-  if (!c || !vol || !agg) return mvs::arg_fail("mvs_sgm_d: null argument");
-  if (bad_dims(W, H) || D < 1) return mvs::arg_fail("mvs_sgm_d: bad dimensions");
-  if (D > mvs::plan::kSgmMaxD) return mvs::arg_fail("mvs_sgm_d: more than 16384 levels");
-  if (paths < 1 || paths > 15) return mvs::arg_fail("mvs_sgm_d: paths must be a mask in 1..15");
+// mvs_sgm_d (masks to 15) and mvs_sgm8_d (to 255): one set of argument rules, the message names the entry point
+static int sgm_call(const char* fn, int max_paths, mvs_ctx* c, int W, int H, int D, const float* vol, float P1,
+                    float P2, int paths, float* agg) {
+  const auto fail = [fn](const std::string& why) { return mvs::arg_fail((std::string(fn) + ": " + why).c_str()); };
+  if (!c || !vol || !agg) return fail("null argument");
+  if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
+  if (D > mvs::plan::kSgmMaxD) return fail("more than 16384 levels");
+  if (paths < 1 || paths > max_paths) return fail("paths must be a mask in 1.." + std::to_string(max_paths));
   // (a NaN fails every comparison)
   if (!(P1 >= 0.0f) || !(P2 >= P1) || !(P2 <= 3.402823466e38f))
-    return mvs::arg_fail("mvs_sgm_d: penalties must be finite with 0 <= P1 <= P2");
-  if (agg == vol) return mvs::arg_fail("mvs_sgm_d: agg must not be vol");
+    return fail("penalties must be finite with 0 <= P1 <= P2");
+  if (agg == vol) return fail("agg must not be vol");
   return mvs::launch_sgm(c->stream, W, H, D, vol, P1, P2, paths, agg);
+}
+
+int mvs_sgm_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
+  return sgm_call("mvs_sgm_d", 15, c, W, H, D, vol, P1, P2, paths, agg);
+}
+
+int mvs_sgm8_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
+  return sgm_call("mvs_sgm8_d", 255, c, W, H, D, vol, P1, P2, paths, agg);
 }
 
 int mvs_ncc_sub_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,

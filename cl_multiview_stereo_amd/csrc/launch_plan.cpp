@@ -415,5 +415,40 @@ SgmPlan plan_sgm(int W, int H, int D, int path) {
   return p;
 }
 
+SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path) {
+  SgmDiagPlan p;
+  if (W < 1 || H < 1 || D < 1 || path < 4 || path > 7) {
+    p.err = "sgm: bad dimensions or path";
+    return p;
+  }
+  if (D > kSgmMaxD) {
+    p.err = "sgm: more than 16384 levels";
+    return p;
+  }
+  p.sx = path < 6 ? 1 : -1;
+  p.rev = path & 1;
+  p.lines = W + H - 1;
+  p.sstride = W + p.sx;
+  if (D <= kSgmColumnsMaxD) {
+    p.form = kSgmSheared;
+    p.lpl = kSgmColumnsLpw;
+    p.waves = (D + kSgmColumnsLpw - 1) / kSgmColumnsLpw;
+    p.grid = (unsigned)((p.lines + 63) / 64);
+    p.lds = sizeof(float) * 2 * (p.waves <= 8 ? 8 : 16) * 3 * 64;  // as the columns form
+  } else {
+    p.form = kSgmLanes;
+    if (D <= kSgmLanesOneWave) {
+      p.lpl = D <= 64 * 8 ? 8 : kSgmMaxLpl;  // (D > 256 here: 8 or 16 levels per lane)
+    } else {
+      p.lpl = kSgmMaxLpl;
+      p.waves = (D + kSgmLanesOneWave - 1) / kSgmLanesOneWave;
+      p.lds = sizeof(float) * 2 * 16 * 3;
+    }
+    p.grid = (unsigned)p.lines;
+  }
+  p.block = 64u * (unsigned)p.waves;
+  return p;
+}
+
 }  // namespace plan
 }  // namespace mvs

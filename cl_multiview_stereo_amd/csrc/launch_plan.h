@@ -242,5 +242,54 @@ struct SgmPlan {
 };
 SgmPlan plan_sgm(int W, int H, int D, int path);
 
+// One diagonal path (include/mvs.h at mvs_sgm8_d): path 4 steps (+1, +1) per
+// pixel, 5 (-1, -1), 6 (-1, +1), 7 (+1, -1).  Paths 4 and 5 walk the W + H - 1
+// lines x - y = const, 6 and 7 the lines x + y = const; along such a line the
+// column moves by sx = +1 (4, 5) or -1 (6, 7) per image row.  4 and 6 walk the
+// rows downwards, 5 and 7 upwards (rev).
+//  * kSgmSheared, k_sgm_diag, D <= kSgmColumnsMaxD: the columns form, sheared.
+//    Workgroup g takes 64 consecutive lines, one per lane; at image row y the
+//    lane stands on column sgm_diag_x0(g, lane, H, sx) + sx * y and is live
+//    there iff that lies in [0, W).  The workgroup walks the rows
+//    [sgm_diag_ylo, sgm_diag_yhi], the rows at which some lane is live, in the
+//    path's order; levels over the waves as in the columns form.
+//  * kSgmLanes, k_sgm_lanes<lpl, false, waves > 1, true> above: one workgroup
+//    per line; sgm_diag_line gives the line's topmost pixel and its length,
+//    and its elements are sstride = W + sx apart.
+constexpr int kSgmSheared = 2;
+constexpr int sgm_diag_x0(int g, int lane, int H, int sx) { return sx > 0 ? 64 * g - (H - 1) + lane : 64 * g + lane; }
+constexpr int sgm_diag_ylo(int g, int W, int H, int sx) {
+  const int y = sx > 0 ? H - 1 - 64 * g - 63 : 64 * g - (W - 1);
+  return y > 0 ? y : 0;
+}
+constexpr int sgm_diag_yhi(int g, int W, int H, int sx) {
+  const int y = sx > 0 ? W + H - 2 - 64 * g : 64 * g + 63;
+  return y < H - 1 ? y : H - 1;
+}
+struct SgmDiagLine {
+  int first, n;  // the topmost pixel's offset in a plane; pixels on the line
+};
+// line l in [0, W + H - 1): x - y = l - (H - 1) for sx = +1, x + y = l for sx = -1
+constexpr SgmDiagLine sgm_diag_line(int W, int H, int sx, int l) {
+  const int c = l - (H - 1);
+  const int xt = sx > 0 ? (c > 0 ? c : 0) : (l < W ? l : W - 1);
+  const int yt = sx > 0 ? (c < 0 ? -c : 0) : (l < W ? 0 : l - (W - 1));
+  const int nx = sx > 0 ? W - xt : xt + 1, ny = H - yt;
+  return {yt * W + xt, nx < ny ? nx : ny};
+}
+struct SgmDiagPlan {
+  const char* err = nullptr;  // the argument error, if any
+  int form = kSgmSheared;
+  int sx = 0;          // the column's step per image row
+  bool rev = false;    // walk from the last row (sheared) or the line's last element (lanes) down
+  int lpl = 1;         // levels per wave (sheared form) or per lane (lanes form)
+  int waves = 1;       // per workgroup
+  int lines = 0;       // W + H - 1
+  int sstride = 0;     // lanes form: W + sx
+  unsigned grid = 0, block = 0;
+  size_t lds = 0;      // static LDS of the kernel form, bytes
+};
+SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path);
+
 }  // namespace plan
 }  // namespace mvs

@@ -129,7 +129,8 @@ int launch_wta_sub(hipStream_t s, int W, int H, int D, const float* vol, const f
 int launch_ncc_sub(hipStream_t s, int V, int W, int H, const int32_t* box, const float* levels_dev, int D,
                    const int* vs_dev, const int* sn_dev, int aw, float bl, int K, int z0, int z1, const float* disp,
                    float* disp_sub);
-// semi-global aggregation (sgm.hip): the set paths of `paths` in bit order, the first stores agg, the others add
+// semi-global aggregation (sgm.hip): the set paths of `paths` (bits 0..7) in bit order, the first stores agg, the
+// others add
 int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg);
 
 int launch_flatness(hipStream_t s, int V, int mw, int mh, const float* spixl, float gamma, float* flat);

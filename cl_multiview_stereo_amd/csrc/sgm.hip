@@ -1,5 +1,6 @@
 // Semi-global aggregation of a cost volume vol [D][H][W] along the four
-// axis-aligned paths (include/mvs.h at mvs_sgm_d; tests/sgm_ref.py).
+// axis-aligned paths (include/mvs.h at mvs_sgm_d; tests/sgm_ref.py) and the
+// four diagonal ones (mvs_sgm8_d).
 //
 // Definition, float32, every operation rounded (there is no multiply, so
 // nothing can fuse).  q is the pixel before p on the path:
@@ -39,6 +40,14 @@
 //    exchange {chunk minimum, first, last} per column through LDS,
 //    double-buffered: one barrier per row.  The next row's costs and agg
 //    are loaded before the waves meet and before this row's stores.
+//  * k_sgm_diag: the four diagonal paths of mvs_sgm8_d (bits 4..7: steps
+//    (+1, +1), (-1, -1), (-1, +1), (+1, -1) per pixel; tests/sgm8_ref.py) at
+//    D <= 256: k_sgm_columns with its band of 64 columns moving by one column
+//    per row, so that a lane follows one diagonal line and its state never
+//    leaves the lane.  A level's row piece is still one coalesced 256 bytes;
+//    its start moves by one float per row and is not aligned.  Above 256 levels
+//    a diagonal line is a strided line of k_sgm_lanes (DIAG), one workgroup per
+//    line, elements W + 1 or W - 1 apart.
 // Plane bases are 64-bit, offsets within a plane 32-bit (W H <= 2^27).
 #include "mvs_internal.h"
 
@@ -89,13 +98,23 @@ __device__ __forceinline__ void sgm_step(float (&L)[NL], const float (&c)[NL], f
   }
 }
 
-template <int LPL, bool VEC, bool MW>
+// DIAG (not VEC): line blockIdx.x of the W + H - 1 diagonal lines with elements sstride = W +- 1 apart; its first
+// element and its length come from the line index (plan::sgm_diag_line), and the arguments n and lstride carry W
+// and H instead.
+template <int LPL, bool VEC, bool MW, bool DIAG = false>
 __global__ __launch_bounds__(MW ? 1024 : 64) void k_sgm_lanes(const float* __restrict__ vol, float* __restrict__ agg,
                                                               int D, long HW, int n, int sstride, int lstride,
                                                               int rev, int acc, float P1, float P2) {
+  static_assert(!(DIAG && VEC), "a diagonal line is not contiguous");
   const int lane = threadIdx.x & 63;
   const int d0 = (int)threadIdx.x * LPL;  // the lane's first level; levels >= D are padding and touch no memory
-  const long base = (long)d0 * HW + (long)((unsigned)blockIdx.x * (unsigned)lstride);
+  long first = (long)((unsigned)blockIdx.x * (unsigned)lstride);
+  if constexpr (DIAG) {
+    const plan::SgmDiagLine ln = plan::sgm_diag_line(n, lstride, sstride - n, (int)blockIdx.x);
+    first = ln.first;
+    n = ln.n;  // (uniform over the workgroup: every wave meets every barrier)
+  }
+  const long base = (long)d0 * HW + first;
   const float* vp = vol + base;
   float* ap = agg + base;
   const int jl = rev ? 3 : 0, js = rev ? 0 : 3;  // the element at which the walk enters / leaves a piece
@@ -270,6 +289,84 @@ __global__ __launch_bounds__(NT) void k_sgm_columns(const float* __restrict__ vo
   }
 }
 
+// Diagonal paths at D <= 256: k_sgm_columns, sheared.  Lane `lane` of workgroup g follows one diagonal line: at
+// image row y it stands on column x0 + sx y (launch_plan.h at plan_sgm_diag) and is live there iff that lies in
+// [0, W).  Along the walk a lane is live on one run of rows: its first live row is the first pixel of its path
+// (L = cost, never a step from what it held outside), and once it has left the image it stays out; it stores
+// on its live rows only.  The rows [ylo, yhi] at which some lane is live are uniform over the workgroup, so
+// every wave meets every barrier.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_sgm_diag(const float* __restrict__ vol, float* __restrict__ agg, int D, int W,
+                                                 int H, int sx, int rev, int acc, float P1, float P2) {
+  __shared__ float ex[2][NT / 64][3][64];  // per wave and line: {chunk minimum, first level, last level}
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int g = blockIdx.x;
+  const int x0 = plan::sgm_diag_x0(g, lane, H, sx);
+  const int ylo = plan::sgm_diag_ylo(g, W, H, sx), n = plan::sgm_diag_yhi(g, W, H, sx) - ylo + 1;
+  const long HW = (long)W * H;
+  const int dw = w * LPW;
+  const float* vw = vol + (long)dw * HW;
+  float* aw = agg + (long)dw * HW;
+  float L[LPW], c[LPW], a[LPW];
+  // Row y's own column.  A lane outside the image reads the row's nearest pixel instead of nothing: what it
+  // holds is never stored and never reaches a live state (`was` below), and with no lane-dependent condition
+  // around or behind a load nothing waits for one before the row after uses it (a select on `in` behind each
+  // load made every load wait for itself: 9.2 ms per path at 1080p, D = 128, against 2.4 ms)
+  const auto load = [&](const float* pl, int y, float(&cc)[LPW], float pad) {
+    const int off = y * W + min(max(x0 + sx * y, 0), W - 1);
+#pragma unroll
+    for (int k = 0; k < LPW; k++) {
+      cc[k] = pad;
+      if (dw + k < D) cc[k] = pl[(long)k * HW + off];
+    }
+  };
+  const int dy = rev ? -1 : 1;
+  int y = rev ? ylo + n - 1 : ylo;
+  bool was = false;  // the lane was live on the row before: this row steps from it
+  load(vw, y, c, SGM_INF);
+  if (acc) load(aw, y, a, 0.0f);
+  for (int i = 0; i < n; i++, y += dy) {
+    // as in k_sgm_columns: the next row's loads before the waves meet and before this row's stores
+    float cn[LPW], an[LPW];
+    if (i + 1 < n) {
+      load(vw, y + dy, cn, SGM_INF);
+      if (acc) load(aw, y + dy, an, 0.0f);
+    }
+    const int x = x0 + sx * y;
+    const bool in = x >= 0 && x < W;
+    if (i > 0) {  // (on the first row no lane has a pixel before it)
+      const int par = i & 1;
+      float m = L[0];
+#pragma unroll
+      for (int k = 1; k < LPW; k++) m = fminf(m, L[k]);
+      ex[par][w][0][lane] = m;
+      ex[par][w][1][lane] = L[0];
+      ex[par][w][2][lane] = L[LPW - 1];
+      // a wave writes buffer par again two rows on, past the next barrier: every wave has read this one by then
+      __syncthreads();
+      m = ex[par][0][0][lane];
+      for (int v = 1; v < nw; v++) m = fminf(m, ex[par][v][0][lane]);
+      const float up = w > 0 ? ex[par][w - 1][2][lane] : SGM_INF;
+      const float dn = w + 1 < nw ? ex[par][w + 1][1][lane] : SGM_INF;
+      sgm_step<LPW>(L, c, up, dn, m, P1, P2);
+    }
+#pragma unroll
+    for (int k = 0; k < LPW; k++) L[k] = was ? L[k] : c[k];
+    was = in;
+    const int off = y * W + x;
+#pragma unroll
+    for (int k = 0; k < LPW; k++)
+      if (in && dw + k < D) aw[(long)k * HW + off] = acc ? a[k] + L[k] : L[k];
+    if (i + 1 < n) {
+#pragma unroll
+      for (int k = 0; k < LPW; k++) {
+        c[k] = cn[k];
+        if (acc) a[k] = an[k];
+      }
+    }
+  }
+}
+
 template <bool VEC, bool MW>
 void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const float* vol, float* agg, int D, long HW, int acc,
                   float P1, float P2) {
@@ -288,6 +385,34 @@ void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const float* vol, float
     }
   }
 #undef SGM_LANES
+}
+
+// one diagonal path (4..7)
+int launch_diag(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int path, int acc,
+                float* agg) {
+  const plan::SgmDiagPlan p = plan::plan_sgm_diag(W, H, D, path);
+  if (p.err) return arg_fail(p.err);
+  const long HW = (long)W * H;
+#define SGM_DIAG_LANES(LPL, MW)                                                                                  \
+  hipLaunchKernelGGL((k_sgm_lanes<LPL, false, MW, true>), dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, HW, W, \
+                     p.sstride, H, (int)p.rev, acc, P1, P2)
+  if (p.form == plan::kSgmSheared) {
+    if (p.block <= 512)
+      hipLaunchKernelGGL(k_sgm_diag<512>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, p.sx, (int)p.rev, acc, P1,
+                         P2);
+    else
+      hipLaunchKernelGGL(k_sgm_diag<1024>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, p.sx, (int)p.rev, acc,
+                         P1, P2);
+  } else if (p.waves > 1) {
+    SGM_DIAG_LANES(16, true);
+  } else if (p.lpl == 8) {
+    SGM_DIAG_LANES(8, false);
+  } else {
+    SGM_DIAG_LANES(16, false);
+  }
+#undef SGM_DIAG_LANES
+  MVS_LAUNCH_CHECK("k_sgm");
+  return 0;
 }
 
 }  // namespace
@@ -314,6 +439,11 @@ int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, f
       launch_lanes<false, false>(s, p, vol, agg, D, HW, acc, P1, P2);
     }
     MVS_LAUNCH_CHECK("k_sgm");
+    acc = 1;
+  }
+  for (int path = 4; path < 8; path++) {
+    if (!((paths >> path) & 1)) continue;
+    if (const int rc = launch_diag(s, W, H, D, vol, P1, P2, path, acc, agg)) return rc;
     acc = 1;
   }
   return 0;

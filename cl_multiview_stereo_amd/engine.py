@@ -325,16 +325,18 @@ class Engine:
 
     def sgm(self, vol, P1: float = 0.1, P2: float = 0.8, paths: int = 15, out=None):
         """Semi-global aggregation of a volume [D, H, W] (include/mvs.h at mvs_sgm_d): the path
-        costs of the paths in the mask (1 left->right, 2 right->left, 4 top->bottom, 8 bottom->top)
-        summed in bit order into out [D, H, W], which must not be vol.  wta on the result gives the
-        aggregated disparity and confidence."""
+        costs of the paths in the mask (1 left->right, 2 right->left, 4 top->bottom, 8 bottom->top;
+        16 down-right, 32 up-left, 64 down-left, 128 up-right: mvs_sgm8_d, called for masks above
+        15 only) summed in bit order into out [D, H, W], which must not be vol.  wta on the result
+        gives the aggregated disparity and confidence."""
         D, H, W = vol.shape
         out = self.empty((D, H, W), torch.float32) if out is None else out
         if tuple(out.shape) != (D, H, W) or vol.dtype != torch.float32 or out.dtype != torch.float32:
             raise ValueError("sgm: vol and out must be float32 [D, H, W]")
         self._stream()
-        _lib.check(self.L.mvs_sgm_d(self.ctx, W, H, D, _ptr(vol), C.c_float(P1), C.c_float(P2), int(paths),
-                                    _ptr(out)), "mvs_sgm_d")
+        name = "mvs_sgm_d" if int(paths) <= 15 else "mvs_sgm8_d"
+        _lib.check(getattr(self.L, name)(self.ctx, W, H, D, _ptr(vol), C.c_float(P1), C.c_float(P2), int(paths),
+                                         _ptr(out)), name)
         return out
 
     def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):

@@ -66,21 +66,25 @@ class PixelSweep:
     the sub-level disparity (the parabola fit of include/mvs.h) of the views
     it swept in self.disp_sub; disp and conf are unchanged.  sgm=True (NCC
     only): run() also leaves the winner and confidence of the semi-globally
-    aggregated volume (mvs_sgm_d, all four paths, penalties sgm_p1 <= sgm_p2)
-    in self.disp_agg and self.conf_agg [z1 - z0, H, W]: per view ncc_volume ->
+    aggregated volume (mvs_sgm_d, penalties sgm_p1 <= sgm_p2; sgm_paths is the
+    path mask, 15 = the four axis-aligned paths, 255 = with the four diagonal
+    ones, mvs_sgm8_d) in self.disp_agg and self.conf_agg [z1 - z0, H, W]:
+    per view ncc_volume ->
     sgm -> wta, through one more [D, H, W] buffer; with fused=True the volume
     is computed for this alone.  disp, conf and disp_sub are unchanged."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
                  fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
-                 sgm_p2: float = 0.8):
+                 sgm_p2: float = 0.8, sgm_paths: int = 15):
         if subpixel and cost != "ncc":
             raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
         if sgm and cost != "ncc":
             raise ValueError("sgm=True needs cost=\"ncc\": the aggregation runs on the NCC cost volume")
+        if not 1 <= int(sgm_paths) <= 255:
+            raise ValueError("sgm_paths must be a path mask in 1..255")
         self.e, self.cam, self.W, self.H = engine, cam, W, H
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
-        self.sgm, self.sgm_p1, self.sgm_p2 = sgm, sgm_p1, sgm_p2
+        self.sgm, self.sgm_p1, self.sgm_p2, self.sgm_paths = sgm, sgm_p1, sgm_p2, int(sgm_paths)
         self.disp_sub = None
         self.disp_agg = self.conf_agg = None
         self.vol = self.agg = None
@@ -130,7 +134,7 @@ class PixelSweep:
 
     def _aggregate(self, i: int):
         """self.vol -> sgm -> wta into view i of disp_agg / conf_agg."""
-        self.e.sgm(self.vol, self.sgm_p1, self.sgm_p2, out=self.agg)
+        self.e.sgm(self.vol, self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg)
         self.e.wta(self.agg, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
 
@@ -188,7 +192,8 @@ class Pipeline:
     def __init__(self, engine: Engine, settings: params.Settings, W: int, H: int,
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
                  refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
-                 subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8):
+                 subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8,
+                 sgm_paths: int = 15):
         self.e, self.st, self.W, self.H = engine, settings, W, H
         vs = view_subset if view_subset is not None else params.neighbour_lists(
             settings.array_width, settings.array_height, settings.neib_hor, settings.neib_ver)
@@ -202,7 +207,7 @@ class Pipeline:
         if sgm and pixel_cost != "ncc":
             raise ValueError("sgm=True needs pixel_cost=\"ncc\"")
         self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
-                                 sgm_p2)
+                                 sgm_p2, sgm_paths)
                       if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None

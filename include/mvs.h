@@ -232,6 +232,24 @@ int mvs_ncc_sub_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int
  * 1..15, a penalty that is not finite, negative, or P1 > P2, agg == vol (the
  * two must not overlap at all).  Nothing is allocated. */
 int mvs_sgm_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg);
+/* The same with the four diagonal paths as well (0.9.1.1).  The recurrence, the
+ * treatment of the levels that do not exist and the rounding are mvs_sgm_d's;
+ * paths is a mask in 1..255, bits 0..3 as above and
+ *   bit 4: a step of (dx, dy) = (+1, +1) per pixel, down-right
+ *   bit 5: (-1, -1), up-left   (bit 4's lines walked the other way)
+ *   bit 6: (-1, +1), down-left
+ *   bit 7: (+1, -1), up-right  (bit 6's lines walked the other way)
+ * A diagonal path visits (x0 + i dx, y0 + i dy), i = 0, 1, ..; its first pixel
+ * is a pixel whose predecessor (x - dx, y - dy) lies outside the image, and
+ * there L = vol.  There are W + H - 1 lines per direction, of 1 .. min(W, H)
+ * pixels; with W == 1 or H == 1 every diagonal line is one pixel and L is vol.
+ *   agg = ((((((L_b0 + L_b1) + L_b2) + L_b3) + L_b4) + L_b5) + L_b6) + L_b7
+ * over the set bits, in bit order, rounded after each add; the first set path
+ * is stored as it is.  For paths <= 15 the result is mvs_sgm_d's, bit for bit,
+ * through the same launches.  MVS_E_ARG as mvs_sgm_d, with paths outside
+ * 1..255.  Nothing is allocated.  mvs_sgm_d itself keeps refusing masks above
+ * 15. */
+int mvs_sgm8_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg);
 /* Tuning / test hook: the NCC sweep variant this context tries first (0 =
  * automatic): waves per workgroup 4|8, levels per wave 1|2|4,
  * minimum LDS band width 64|80|96|128|192|256 columns, general_rows 1 = the kernel
