@@ -23,7 +23,7 @@ EXPORTS = [
     "mvs_do_super_pixel_seg", "mvs_do_initial_depth_estimation", "mvs_do_refinement", "mvs_do_consistency_filter",
     "mvs_init_state_range_l16_d", "mvs_propagate_l16_d", "mvs_spixl_to_image_l16_d",
     "mvs_wta_sub_d", "mvs_ncc_sub_range_d",
-    "mvs_sgm_d", "mvs_sgm8_d",
+    "mvs_sgm_d", "mvs_sgm8_d", "mvs_sgm8_batch_d",
 ]
 
 
@@ -76,6 +76,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     L.mvs_sgm8_d.restype = C.c_int
     L.mvs_sgm8_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int,
                              C.c_void_p]
+    L.mvs_sgm8_batch_d.restype = C.c_int
+    L.mvs_sgm8_batch_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_float,
+                                   C.c_float, C.c_int, C.c_void_p, C.c_size_t]
     _lib = L
     return L
 

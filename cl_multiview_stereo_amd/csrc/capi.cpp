@@ -158,7 +158,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1.1 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -368,9 +368,11 @@ int mvs_wta_sub_d(mvs_ctx* c, int W, int H, int D, const float* vol, const float
   return mvs::launch_wta_sub(c->stream, W, H, D, vol, levels, disp_sub);
 }
 
-// mvs_sgm_d (masks to 15) and mvs_sgm8_d (to 255): one set of argument rules, the message names the entry point
+// mvs_sgm_d (masks to 15), mvs_sgm8_d (to 255) and mvs_sgm8_batch_d (batch: N volumes, strides and the span rule of
+// plan_sgm_batch): one set of argument rules, the message names the entry point
 static int sgm_call(const char* fn, int max_paths, mvs_ctx* c, int W, int H, int D, const float* vol, float P1,
-                    float P2, int paths, float* agg) {
+                    float P2, int paths, float* agg, bool batch = false, int N = 1, size_t vol_stride = 0,
+                    size_t agg_stride = 0) {
   const auto fail = [fn](const std::string& why) { return mvs::arg_fail((std::string(fn) + ": " + why).c_str()); };
   if (!c || !vol || !agg) return fail("null argument");
   if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
@@ -379,8 +381,14 @@ static int sgm_call(const char* fn, int max_paths, mvs_ctx* c, int W, int H, int
   // (a NaN fails every comparison)
   if (!(P1 >= 0.0f) || !(P2 >= P1) || !(P2 <= 3.402823466e38f))
     return fail("penalties must be finite with 0 <= P1 <= P2");
-  if (agg == vol) return fail("agg must not be vol");
-  return mvs::launch_sgm(c->stream, W, H, D, vol, P1, P2, paths, agg);
+  if (batch) {
+    const mvs::plan::SgmBatchPlan b =
+        mvs::plan::plan_sgm_batch(W, H, D, N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
+    if (b.err) return fail(b.err);
+  } else if (agg == vol) {
+    return fail("agg must not be vol");
+  }
+  return mvs::launch_sgm(c->stream, W, H, D, N, vol, vol_stride, P1, P2, paths, agg, agg_stride);
 }
 
 int mvs_sgm_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
@@ -389,6 +397,11 @@ int mvs_sgm_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float
 
 int mvs_sgm8_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
   return sgm_call("mvs_sgm8_d", 255, c, W, H, D, vol, P1, P2, paths, agg);
+}
+
+int mvs_sgm8_batch_d(mvs_ctx* c, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
+                     int paths, float* agg, size_t agg_stride) {
+  return sgm_call("mvs_sgm8_batch_d", 255, c, W, H, D, vol, P1, P2, paths, agg, true, N, vol_stride, agg_stride);
 }
 
 int mvs_ncc_sub_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,

@@ -291,5 +291,26 @@ struct SgmDiagPlan {
 };
 SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path);
 
+// N volumes of one shape per launch (include/mvs.h at mvs_sgm8_batch_d): element i is the volume at
+// vol + i * vol_stride and its aggregate at agg + i * agg_stride (addresses in bytes, strides in floats).  The
+// batch index is the grid's second axis, so every launch of plan_sgm / plan_sgm_diag becomes (grid, grid_y).
+//  * err: N outside 1..kSgmMaxBatch, a stride below D H W, or the two spans
+//    [addr, addr + 4 ((N - 1) stride + D H W)) overlap (abutting spans do not); also bad dimensions.
+//  * vec_ok: the 16-byte-pieces form of k_sgm_lanes needs vol and agg equal mod 16 bytes in every element: the
+//    bases are, and with N > 1 the strides differ by a multiple of 4 floats.  (The strides themselves need be
+//    no multiple of 4: a (lane, level)'s phase comes from its real address.)  Else the whole batch takes the
+//    scalar form.
+constexpr int kSgmMaxBatch = 65535;  // one grid axis
+struct SgmBatchPlan {
+  const char* err = nullptr;  // the argument error, if any
+  unsigned grid_y = 0;
+  bool vec_ok = false;
+};
+constexpr bool sgm_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
+  return ((vol_addr ^ agg_addr) & 15) == 0 && (N == 1 || ((vol_stride - agg_stride) & 3) == 0);
+}
+SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
+                            size_t agg_stride);
+
 }  // namespace plan
 }  // namespace mvs

@@ -130,8 +130,10 @@ int launch_ncc_sub(hipStream_t s, int V, int W, int H, const int32_t* box, const
                    const int* vs_dev, const int* sn_dev, int aw, float bl, int K, int z0, int z1, const float* disp,
                    float* disp_sub);
 // semi-global aggregation (sgm.hip): the set paths of `paths` (bits 0..7) in bit order, the first stores agg, the
-// others add
-int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg);
+// others add; N volumes per launch, element i at vol + i * vol_stride and agg + i * agg_stride (floats; the
+// strides are not read at N = 1)
+int launch_sgm(hipStream_t s, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
+               int paths, float* agg, size_t agg_stride);
 
 int launch_flatness(hipStream_t s, int V, int mw, int mh, const float* spixl, float gamma, float* flat);
 // labels: uint32, or uint16 when lbits == 16 (16-bit gathered maps)

@@ -49,6 +49,11 @@
 //    a diagonal line is a strided line of k_sgm_lanes (DIAG), one workgroup per
 //    line, elements W + 1 or W - 1 apart.
 // Plane bases are 64-bit, offsets within a plane 32-bit (W H <= 2^27).
+//
+// Every form takes N volumes of one shape per launch (mvs_sgm8_batch_d): the
+// batch index is blockIdx.y, and a kernel first moves its two bases to its
+// element (blockIdx.y * stride, 64-bit); nothing else knows of the batch.  The
+// single-volume entry points launch with N = 1.
 #include "mvs_internal.h"
 
 namespace mvs {
@@ -103,9 +108,12 @@ __device__ __forceinline__ void sgm_step(float (&L)[NL], const float (&c)[NL], f
 // and H instead.
 template <int LPL, bool VEC, bool MW, bool DIAG = false>
 __global__ __launch_bounds__(MW ? 1024 : 64) void k_sgm_lanes(const float* __restrict__ vol, float* __restrict__ agg,
-                                                              int D, long HW, int n, int sstride, int lstride,
-                                                              int rev, int acc, float P1, float P2) {
+                                                              size_t vstride, size_t astride, int D, long HW, int n,
+                                                              int sstride, int lstride, int rev, int acc, float P1,
+                                                              float P2) {
   static_assert(!(DIAG && VEC), "a diagonal line is not contiguous");
+  vol += (size_t)blockIdx.y * vstride;  // the batch element: 64-bit, before anything is derived from the bases
+  agg += (size_t)blockIdx.y * astride;
   const int lane = threadIdx.x & 63;
   const int d0 = (int)threadIdx.x * LPL;  // the lane's first level; levels >= D are padding and touch no memory
   long first = (long)((unsigned)blockIdx.x * (unsigned)lstride);
@@ -225,8 +233,11 @@ constexpr int LPW = plan::kSgmColumnsLpw;
 
 // NT: the workgroup's thread limit (512 up to 8 waves: 128 levels)
 template <int NT>
-__global__ __launch_bounds__(NT) void k_sgm_columns(const float* __restrict__ vol, float* __restrict__ agg, int D, int W,
-                                                    int H, int rev, int acc, float P1, float P2) {
+__global__ __launch_bounds__(NT) void k_sgm_columns(const float* __restrict__ vol, float* __restrict__ agg,
+                                                    size_t vstride, size_t astride, int D, int W, int H, int rev,
+                                                    int acc, float P1, float P2) {
+  vol += (size_t)blockIdx.y * vstride;  // the batch element
+  agg += (size_t)blockIdx.y * astride;
   __shared__ float ex[2][NT / 64][3][64];  // per wave and column: {chunk minimum, first level, last level}
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int x = blockIdx.x * 64 + lane;
@@ -296,8 +307,11 @@ __global__ __launch_bounds__(NT) void k_sgm_columns(const float* __restrict__ vo
 // on its live rows only.  The rows [ylo, yhi] at which some lane is live are uniform over the workgroup, so
 // every wave meets every barrier.
 template <int NT>
-__global__ __launch_bounds__(NT) void k_sgm_diag(const float* __restrict__ vol, float* __restrict__ agg, int D, int W,
-                                                 int H, int sx, int rev, int acc, float P1, float P2) {
+__global__ __launch_bounds__(NT) void k_sgm_diag(const float* __restrict__ vol, float* __restrict__ agg,
+                                                 size_t vstride, size_t astride, int D, int W, int H, int sx, int rev,
+                                                 int acc, float P1, float P2) {
+  vol += (size_t)blockIdx.y * vstride;  // the batch element
+  agg += (size_t)blockIdx.y * astride;
   __shared__ float ex[2][NT / 64][3][64];  // per wave and line: {chunk minimum, first level, last level}
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int g = blockIdx.x;
@@ -367,12 +381,21 @@ __global__ __launch_bounds__(NT) void k_sgm_diag(const float* __restrict__ vol, 
   }
 }
 
+// The batch of a launch: N elements on the grid's second axis, element i at vol + i vstride, agg + i astride.
+struct SgmBatch {
+  unsigned N;
+  const float* vol;
+  size_t vstride;
+  float* agg;
+  size_t astride;
+};
+
 template <bool VEC, bool MW>
-void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const float* vol, float* agg, int D, long HW, int acc,
-                  float P1, float P2) {
-#define SGM_LANES(LPL)                                                                                            \
-  hipLaunchKernelGGL((k_sgm_lanes<LPL, VEC, MW>), dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, HW, p.n, p.sstride, \
-                     p.lstride, (int)p.rev, acc, P1, P2)
+void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const SgmBatch& b, int D, long HW, int acc, float P1,
+                  float P2) {
+#define SGM_LANES(LPL)                                                                                          \
+  hipLaunchKernelGGL((k_sgm_lanes<LPL, VEC, MW>), dim3(p.grid, b.N), dim3(p.block), 0, s, b.vol, b.agg, b.vstride, \
+                     b.astride, D, HW, p.n, p.sstride, p.lstride, (int)p.rev, acc, P1, P2)
   if constexpr (MW) {
     SGM_LANES(16);
   } else {
@@ -388,21 +411,21 @@ void launch_lanes(hipStream_t s, const plan::SgmPlan& p, const float* vol, float
 }
 
 // one diagonal path (4..7)
-int launch_diag(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int path, int acc,
-                float* agg) {
+int launch_diag(hipStream_t s, int W, int H, int D, const SgmBatch& b, float P1, float P2, int path, int acc) {
   const plan::SgmDiagPlan p = plan::plan_sgm_diag(W, H, D, path);
   if (p.err) return arg_fail(p.err);
   const long HW = (long)W * H;
-#define SGM_DIAG_LANES(LPL, MW)                                                                                  \
-  hipLaunchKernelGGL((k_sgm_lanes<LPL, false, MW, true>), dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, HW, W, \
-                     p.sstride, H, (int)p.rev, acc, P1, P2)
+  const dim3 grid(p.grid, b.N);
+#define SGM_DIAG_LANES(LPL, MW)                                                                                 \
+  hipLaunchKernelGGL((k_sgm_lanes<LPL, false, MW, true>), grid, dim3(p.block), 0, s, b.vol, b.agg, b.vstride,   \
+                     b.astride, D, HW, W, p.sstride, H, (int)p.rev, acc, P1, P2)
   if (p.form == plan::kSgmSheared) {
     if (p.block <= 512)
-      hipLaunchKernelGGL(k_sgm_diag<512>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, p.sx, (int)p.rev, acc, P1,
-                         P2);
+      hipLaunchKernelGGL(k_sgm_diag<512>, grid, dim3(p.block), 0, s, b.vol, b.agg, b.vstride, b.astride, D, W, H, p.sx,
+                         (int)p.rev, acc, P1, P2);
     else
-      hipLaunchKernelGGL(k_sgm_diag<1024>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, p.sx, (int)p.rev, acc,
-                         P1, P2);
+      hipLaunchKernelGGL(k_sgm_diag<1024>, grid, dim3(p.block), 0, s, b.vol, b.agg, b.vstride, b.astride, D, W, H, p.sx,
+                         (int)p.rev, acc, P1, P2);
   } else if (p.waves > 1) {
     SGM_DIAG_LANES(16, true);
   } else if (p.lpl == 8) {
@@ -417,8 +440,12 @@ int launch_diag(hipStream_t s, int W, int H, int D, const float* vol, float P1, 
 
 }  // namespace
 
-int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
+int launch_sgm(hipStream_t s, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
+               int paths, float* agg, size_t agg_stride) {
   const long HW = (long)W * H;
+  const SgmBatch b{(unsigned)N, vol, vol_stride, agg, agg_stride};
+  // 16-byte pieces: vol and agg equal mod 16 bytes in every element of the batch, else the scalar form for all
+  const bool vec_ok = plan::sgm_batch_vec_ok(N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
   int acc = 0;  // the first set path stores, the later ones add
   for (int path = 0; path < 4; path++) {
     if (!((paths >> path) & 1)) continue;
@@ -426,24 +453,24 @@ int launch_sgm(hipStream_t s, int W, int H, int D, const float* vol, float P1, f
     if (p.err) return arg_fail(p.err);
     if (p.form == plan::kSgmColumns) {
       if (p.block <= 512)
-        hipLaunchKernelGGL(k_sgm_columns<512>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, (int)p.rev, acc, P1,
-                           P2);
+        hipLaunchKernelGGL(k_sgm_columns<512>, dim3(p.grid, b.N), dim3(p.block), 0, s, vol, agg, vol_stride, agg_stride,
+                           D, W, H, (int)p.rev, acc, P1, P2);
       else
-        hipLaunchKernelGGL(k_sgm_columns<1024>, dim3(p.grid), dim3(p.block), 0, s, vol, agg, D, W, H, (int)p.rev, acc,
-                           P1, P2);
+        hipLaunchKernelGGL(k_sgm_columns<1024>, dim3(p.grid, b.N), dim3(p.block), 0, s, vol, agg, vol_stride,
+                           agg_stride, D, W, H, (int)p.rev, acc, P1, P2);
     } else if (p.waves > 1) {
-      launch_lanes<false, true>(s, p, vol, agg, D, HW, acc, P1, P2);
-    } else if (p.vec && (((uintptr_t)vol ^ (uintptr_t)agg) & 15) == 0) {
-      launch_lanes<true, false>(s, p, vol, agg, D, HW, acc, P1, P2);
+      launch_lanes<false, true>(s, p, b, D, HW, acc, P1, P2);
+    } else if (p.vec && vec_ok) {
+      launch_lanes<true, false>(s, p, b, D, HW, acc, P1, P2);
     } else {
-      launch_lanes<false, false>(s, p, vol, agg, D, HW, acc, P1, P2);
+      launch_lanes<false, false>(s, p, b, D, HW, acc, P1, P2);
     }
     MVS_LAUNCH_CHECK("k_sgm");
     acc = 1;
   }
   for (int path = 4; path < 8; path++) {
     if (!((paths >> path) & 1)) continue;
-    if (const int rc = launch_diag(s, W, H, D, vol, P1, P2, path, acc, agg)) return rc;
+    if (const int rc = launch_diag(s, W, H, D, b, P1, P2, path, acc)) return rc;
     acc = 1;
   }
   return 0;

@@ -339,6 +339,31 @@ class Engine:
                                          _ptr(out)), name)
         return out
 
+    def sgm_batch(self, vols, P1: float = 0.1, P2: float = 0.8, paths: int = 15, out=None):
+        """sgm of N volumes of one shape in one call (include/mvs.h at mvs_sgm8_batch_d): vols
+        float32 [N, D, H, W], one launch per path over all N; out[i] holds the bits sgm(vols[i])
+        gives.  Each vols[i] is contiguous and stride(0) >= D * H * W (a view into a padded buffer
+        is allowed); out obeys the same rule and must not overlap vols, gaps included.  vols and
+        out together are 2 * N * 4 * D * H * W bytes."""
+        if vols.dim() != 4 or vols.dtype != torch.float32:
+            raise ValueError("sgm_batch: vols must be float32 [N, D, H, W]")
+        N, D, H, W = vols.shape
+        if N < 1:
+            raise ValueError("sgm_batch: vols holds no volume")
+        out = self.empty((N, D, H, W), torch.float32) if out is None else out
+        if tuple(out.shape) != (N, D, H, W) or out.dtype != torch.float32:
+            raise ValueError("sgm_batch: out must be float32 [N, D, H, W]")
+        for t in (vols, out):
+            if not t[0].is_contiguous() or (N > 1 and t.stride(0) < D * H * W):
+                raise ValueError("sgm_batch: every element must be contiguous, with stride(0) >= D * H * W")
+        self._stream()
+        # (at N = 1 a tensor's stride(0) is arbitrary and is not read)
+        vs, os_ = (D * H * W, D * H * W) if N == 1 else (vols.stride(0), out.stride(0))
+        _lib.check(self.L.mvs_sgm8_batch_d(self.ctx, W, H, D, N, _ptr(vols[0]), vs, P1, P2, int(paths), _ptr(out[0]),
+                                           os_),
+                   "mvs_sgm8_batch_d")
+        return out
+
     def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):
         """The same for reference views [z0, z1) without a volume: disp [z1 - z0, H, W] is what
         ncc_wta_range wrote; the three costs are recomputed from the window planes (bit-identical

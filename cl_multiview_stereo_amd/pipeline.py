@@ -71,27 +71,38 @@ class PixelSweep:
     ones, mvs_sgm8_d) in self.disp_agg and self.conf_agg [z1 - z0, H, W]:
     per view ncc_volume ->
     sgm -> wta, through one more [D, H, W] buffer; with fused=True the volume
-    is computed for this alone.  disp, conf and disp_sub are unchanged."""
+    is computed for this alone.  disp, conf and disp_sub are unchanged.
+    sgm_batch=B > 1: the views of a run are aggregated in groups of up to B,
+    one mvs_sgm8_batch_d call per group (one launch per path over the whole
+    group) through [min(B, V), D, H, W] buffers; every output keeps its bits.
+    The two buffers take 2 * B * 4 * D * H * W bytes: 10.6 GB at 1920x1080,
+    D = 128, B = 5.  With 1, the default, allocations and launches are as
+    without the option."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
                  fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
-                 sgm_p2: float = 0.8, sgm_paths: int = 15):
+                 sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1):
         if subpixel and cost != "ncc":
             raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
         if sgm and cost != "ncc":
             raise ValueError("sgm=True needs cost=\"ncc\": the aggregation runs on the NCC cost volume")
         if not 1 <= int(sgm_paths) <= 255:
             raise ValueError("sgm_paths must be a path mask in 1..255")
+        if int(sgm_batch) < 1:
+            raise ValueError("sgm_batch must be at least 1")
         self.e, self.cam, self.W, self.H = engine, cam, W, H
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
         self.sgm, self.sgm_p1, self.sgm_p2, self.sgm_paths = sgm, sgm_p1, sgm_p2, int(sgm_paths)
         self.disp_sub = None
         self.disp_agg = self.conf_agg = None
         self.vol = self.agg = None
+        # views per mvs_sgm8_batch_d call (1: one mvs_sgm_d / mvs_sgm8_d call per view)
+        self.sgm_batch = min(int(sgm_batch), cam.view_count) if sgm else 1
+        shape = (cam.D, H, W) if self.sgm_batch == 1 else (self.sgm_batch, cam.D, H, W)
         if cost == "ncc" and (sgm or not fused):
-            self.vol = engine.empty((cam.D, H, W), torch.float32)
+            self.vol = engine.empty(shape, torch.float32)
         if sgm:
-            self.agg = engine.empty((cam.D, H, W), torch.float32)
+            self.agg = engine.empty(shape, torch.float32)
         self.levels = engine.levels_dev(cam)
 
     def run(self, lab, l8, z0: int, z1: int, disp_out=None, conf_out=None, views=None):
@@ -116,13 +127,18 @@ class PixelSweep:
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
             if self.subpixel:  # the post-pass over the whole range, one call
                 self.disp_sub = self.e.ncc_sub_range(l8, box, self.cam, z0, z1, self.K, disp=disp)
-            if self.sgm:  # the volume the fused sweep never stores, for the aggregation alone
+            if self.sgm_batch > 1:
+                self._run_groups(l8, box, z0, z1, None, None)
+            elif self.sgm:  # the volume the fused sweep never stores, for the aggregation alone
                 for i, z in enumerate(range(z0, z1)):
                     self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
                     self._aggregate(i)
             return disp, conf
         if self.subpixel:
             self.disp_sub = self.e.empty((n, self.H, self.W), torch.float32)
+        if self.sgm_batch > 1:
+            self._run_groups(l8, box, z0, z1, disp, conf)
+            return disp, conf
         for i, z in enumerate(range(z0, z1)):
             self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
             self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
@@ -131,6 +147,25 @@ class PixelSweep:
             if self.sgm:
                 self._aggregate(i)
         return disp, conf
+
+    def _run_groups(self, l8, box, z0: int, z1: int, disp, conf):
+        """sgm_batch > 1: the views of [z0, z1) in groups of at most sgm_batch (the last may be shorter).  Per view
+        of a group ncc_volume into vol[j] (and, in the two-pass form, where disp is given, wta / wta_sub of it), one
+        sgm_batch over the group, then wta of agg[j] into view i of disp_agg / conf_agg."""
+        B = self.sgm_batch
+        for g0 in range(z0, z1, B):
+            g = min(B, z1 - g0)
+            for j in range(g):
+                i = g0 - z0 + j
+                self.e.ncc_volume(l8, box, self.cam, g0 + j, self.K, out=self.vol[j])
+                if disp is not None:
+                    self.e.wta(self.vol[j], self.levels, disp=disp[i], conf=conf[i])
+                    if self.subpixel:
+                        self.e.wta_sub(self.vol[j], self.levels, out=self.disp_sub[i])
+            self.e.sgm_batch(self.vol[:g], self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg[:g])
+            for j in range(g):
+                i = g0 - z0 + j
+                self.e.wta(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
     def _aggregate(self, i: int):
         """self.vol -> sgm -> wta into view i of disp_agg / conf_agg."""
@@ -193,7 +228,10 @@ class Pipeline:
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
                  refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
                  subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8,
-                 sgm_paths: int = 15):
+                 sgm_paths: int = 15, sgm_batch: int = 1):
+        """sgm_batch: see PixelSweep (views aggregated per call; 2 * B * 4 * D * H * W bytes of buffers)."""
+        if int(sgm_batch) < 1:
+            raise ValueError("sgm_batch must be at least 1")
         self.e, self.st, self.W, self.H = engine, settings, W, H
         vs = view_subset if view_subset is not None else params.neighbour_lists(
             settings.array_width, settings.array_height, settings.neib_hor, settings.neib_ver)
@@ -207,7 +245,7 @@ class Pipeline:
         if sgm and pixel_cost != "ncc":
             raise ValueError("sgm=True needs pixel_cost=\"ncc\"")
         self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
-                                 sgm_p2, sgm_paths)
+                                 sgm_p2, sgm_paths, sgm_batch)
                       if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None

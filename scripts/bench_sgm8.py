@@ -13,7 +13,11 @@ mask 4's of this run.
 
 Writes profiles/sgm8/ab.json.
 
-    python scripts/bench_sgm8.py [--calls 20] [--out FILE]
+    python scripts/bench_sgm8.py [--calls 20] [--out FILE] [--masks 1,4,16,15,255]
+
+--masks: other masks than the default set (an A/B of two builds of the library
+through MVS_LIB on a few of them); the ratios and the winners' share are
+written for the masks they need.
 """
 from __future__ import annotations
 
@@ -48,7 +52,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sgm8", "ab.json"))
+    ap.add_argument("--masks", default=",".join(map(str, MASKS)))
     a = ap.parse_args()
+    masks = tuple(int(m) for m in a.masks.split(","))
     cfg = C2
     W, H, aw, D = cfg["W"], cfg["H"], cfg["aw"], cfg["dmax"] + 1
     e = Engine(0)
@@ -68,7 +74,7 @@ def main():
                      "spread; masks up to 15 go through mvs_sgm_d, larger ones through mvs_sgm8_d",
            "bytes_per_pass": unit, "call": {}}
     lev = e.levels_dev(cam)
-    for paths in MASKS:
+    for paths in masks:
         for _ in range(2):
             e.sgm(vol, 0.1, 0.8, paths, out=agg)
         evs = []
@@ -86,11 +92,14 @@ def main():
             s["_win"] = e.wta(agg, lev)[0].clone()
         res["call"][f"paths_{paths}"] = s
         print("call", paths, json.dumps({k: v for k, v in s.items() if k != "_win"}), flush=True)
-    vert = res["call"]["paths_4"]["ms"]
-    for paths in (16, 32, 64, 128):
-        res["call"][f"paths_{paths}"]["ratio_to_vertical"] = round(res["call"][f"paths_{paths}"]["ms"] / vert, 3)
-    w4, w8 = res["call"]["paths_15"].pop("_win"), res["call"]["paths_255"].pop("_win")
-    res["winner_8_paths_differs_from_4_paths_share"] = round(float((w4 != w8).float().mean()), 4)
+    if 4 in masks:
+        vert = res["call"]["paths_4"]["ms"]
+        for paths in (16, 32, 64, 128):
+            if paths in masks:
+                res["call"][f"paths_{paths}"]["ratio_to_vertical"] = round(res["call"][f"paths_{paths}"]["ms"] / vert, 3)
+    wins = [res["call"][f"paths_{m}"].pop("_win") for m in (15, 255) if m in masks]
+    if len(wins) == 2:
+        res["winner_8_paths_differs_from_4_paths_share"] = round(float((wins[0] != wins[1]).float().mean()), 4)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
