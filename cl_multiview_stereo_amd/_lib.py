@@ -24,6 +24,7 @@ EXPORTS = [
     "mvs_init_state_range_l16_d", "mvs_propagate_l16_d", "mvs_spixl_to_image_l16_d",
     "mvs_wta_sub_d", "mvs_ncc_sub_range_d",
     "mvs_sgm_d", "mvs_sgm8_d", "mvs_sgm8_batch_d",
+    "mvs_quant_u16_d", "mvs_sgm8_u16_batch_d", "mvs_wta_u16_d",
 ]
 
 
@@ -79,6 +80,13 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     L.mvs_sgm8_batch_d.restype = C.c_int
     L.mvs_sgm8_batch_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_float,
                                    C.c_float, C.c_int, C.c_void_p, C.c_size_t]
+    L.mvs_quant_u16_d.restype = C.c_int
+    L.mvs_quant_u16_d.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.mvs_sgm8_u16_batch_d.restype = C.c_int
+    L.mvs_sgm8_u16_batch_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    L.mvs_wta_u16_d.restype = C.c_int
+    L.mvs_wta_u16_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -158,7 +158,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1.1 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1.1.1 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -402,6 +402,41 @@ int mvs_sgm8_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, floa
 int mvs_sgm8_batch_d(mvs_ctx* c, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
                      int paths, float* agg, size_t agg_stride) {
   return sgm_call("mvs_sgm8_batch_d", 255, c, W, H, D, vol, P1, P2, paths, agg, true, N, vol_stride, agg_stride);
+}
+
+// the 16-bit aggregation: float32 costs -> uint16, the aggregate of N uint16 volumes, its winner
+int mvs_quant_u16_d(mvs_ctx* c, size_t n, const float* src, uint16_t* dst) {
+  const auto fail = [](const char* why) { return mvs::arg_fail((std::string("mvs_quant_u16_d: ") + why).c_str()); };
+  if (!c || !src || !dst) return fail("null argument");
+  if (((uintptr_t)src & 3) || ((uintptr_t)dst & 1)) return fail("a pointer that is not aligned to its element");
+  {
+    typedef unsigned __int128 u128;
+    const u128 s0 = (uintptr_t)src, s1 = s0 + (u128)4 * n, d0 = (uintptr_t)dst, d1 = d0 + (u128)2 * n;
+    if (s0 < d1 && d0 < s1) return fail("src and dst overlap");
+  }
+  return mvs::launch_quant_u16(c->stream, n, src, dst);
+}
+
+int mvs_sgm8_u16_batch_d(mvs_ctx* c, int W, int H, int D, int N, const uint16_t* vol, size_t vol_stride, int P1, int P2,
+                         int paths, uint16_t* agg, size_t agg_stride) {
+  const auto fail = [](const std::string& why) { return mvs::arg_fail(("mvs_sgm8_u16_batch_d: " + why).c_str()); };
+  if (!c || !vol || !agg) return fail("null argument");
+  if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
+  if (paths < 1 || paths > 255) return fail("paths must be a mask in 1..255");
+  if (P1 < 0 || P2 < P1 || P2 > mvs::plan::kSgm16MaxP) return fail("penalties must obey 0 <= P1 <= P2 <= 4095");
+  const mvs::plan::Sgm16BatchPlan b =
+      mvs::plan::plan_sgm16_batch(W, H, D, N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
+  if (b.err) {
+    fail(b.err);
+    return b.unsupported ? MVS_E_UNSUPPORTED : MVS_E_ARG;
+  }
+  return mvs::launch_sgm16(c->stream, W, H, D, N, vol, vol_stride, P1, P2, paths, agg, agg_stride);
+}
+
+int mvs_wta_u16_d(mvs_ctx* c, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp, float* conf) {
+  if (!c || !agg || !levels || !disp || D <= 0 || bad_dims(W, H) || ((uintptr_t)agg & 1))
+    return mvs::arg_fail("mvs_wta_u16_d: bad arguments");
+  return mvs::launch_wta_u16(c->stream, W, H, D, agg, levels, disp, conf);
 }
 
 int mvs_ncc_sub_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,

@@ -479,5 +479,43 @@ SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size
   return p;
 }
 
+Sgm16BatchPlan plan_sgm16_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
+                                size_t agg_stride) {
+  Sgm16BatchPlan p;
+  if (W < 1 || H < 1 || D < 1 || (long)W * H > (1L << 27)) {
+    p.err = "bad dimensions";
+    return p;
+  }
+  if (D > kSgm16MaxD) {
+    p.err = "more than 256 levels: the 16-bit forms are not built for them";
+    p.unsupported = true;
+    return p;
+  }
+  if (N < 1 || N > kSgmMaxBatch) {
+    p.err = "N must be in 1..65535";
+    return p;
+  }
+  if ((vol_addr | agg_addr) & 1) {
+    p.err = "a pointer that is not 2-byte aligned";
+    return p;
+  }
+  const size_t dhw = (size_t)D * (size_t)H * (size_t)W;  // <= 2^35
+  if (vol_stride < dhw || agg_stride < dhw) {
+    p.err = "a stride below D*H*W";
+    return p;
+  }
+  // the spans in bytes; 128 bits: a stride is any size_t
+  typedef unsigned __int128 u128;
+  const u128 v0 = vol_addr, v1 = v0 + 2 * ((u128)(N - 1) * vol_stride + dhw);
+  const u128 a0 = agg_addr, a1 = a0 + 2 * ((u128)(N - 1) * agg_stride + dhw);
+  if (v0 < a1 && a0 < v1) {
+    p.err = "the vol and agg spans overlap";
+    return p;
+  }
+  p.grid_y = (unsigned)N;
+  p.vec_ok = sgm16_batch_vec_ok(N, vol_addr, vol_stride, agg_addr, agg_stride);
+  return p;
+}
+
 }  // namespace plan
 }  // namespace mvs

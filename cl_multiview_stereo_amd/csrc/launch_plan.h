@@ -312,5 +312,38 @@ constexpr bool sgm_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, ui
 SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
                             size_t agg_stride);
 
+// ---- launch_sgm16 (sgm16.hip) -----------------------------------------------
+// The same aggregation on 16-bit integer costs (include/mvs.h at mvs_sgm8_u16_batch_d).  The geometry of a path is
+// plan_sgm's and plan_sgm_diag's as they are (D <= kSgm16MaxD: the lanes form with 1, 2 or 4 levels per lane and
+// one wave for the horizontal paths, the columns form for the vertical ones, the sheared form for the diagonal
+// ones); what differs is counted in 2-byte elements:
+//  * err: as plan_sgm_batch, with the spans [addr, addr + 2 ((N - 1) stride + D H W)) and an address that is
+//    no multiple of 2 refused.  unsupported (with err set): D > kSgm16MaxD.
+//  * vec_ok: the 16-byte-pieces form needs vol and agg equal mod 16 bytes in every element: the bases are, and
+//    with N > 1 the strides differ by a multiple of 8 elements.  Else the whole batch takes the 2-byte form.
+//  * sgm16_phase: a piece holds eight pixels.  For a (lane, level) whose line starts at byte address a, pixel x
+//    is element j = (x + ph) mod 8, ph = (a / 2) mod 8, of the piece of pixels x - j .. x - j + 7, which starts
+//    at a multiple of 16 bytes; sgm16_piece_inside says whether that piece lies inside the line of n pixels (it
+//    is then read and written whole; else its pixels are handled one by one).
+constexpr int kSgm16MaxD = kSgmColumnsMaxD;  // 256 levels: the forms for more are left out
+constexpr int kSgm16MaxCost = 4094, kSgm16MaxP = 4095;
+constexpr int kSgm16Piece = 8;  // pixels per 16-byte piece
+struct Sgm16BatchPlan {
+  const char* err = nullptr;  // the argument error, if any
+  bool unsupported = false;   // err is "more levels than the 16-bit forms take"
+  unsigned grid_y = 0;
+  bool vec_ok = false;
+};
+constexpr bool sgm16_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
+  return ((vol_addr ^ agg_addr) & 15) == 0 && (N == 1 || ((vol_stride - agg_stride) & 7) == 0);
+}
+constexpr int sgm16_phase(uintptr_t line_addr) { return (int)((line_addr >> 1) & 7); }
+constexpr int sgm16_piece_elem(int ph, int x) { return (x + ph) & 7; }
+constexpr bool sgm16_piece_inside(int ph, int x, int n) {
+  return x - sgm16_piece_elem(ph, x) >= 0 && x - sgm16_piece_elem(ph, x) + 7 < n;
+}
+Sgm16BatchPlan plan_sgm16_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
+                                size_t agg_stride);
+
 }  // namespace plan
 }  // namespace mvs

@@ -134,6 +134,14 @@ int launch_ncc_sub(hipStream_t s, int V, int W, int H, const int32_t* box, const
 // strides are not read at N = 1)
 int launch_sgm(hipStream_t s, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
                int paths, float* agg, size_t agg_stride);
+// the same on 16-bit integer costs (sgm16.hip; include/mvs.h at mvs_sgm8_u16_batch_d): D <= 256, strides in
+// 2-byte elements, the sum over the set paths exact; the quantiser that makes such a volume and the winner pass
+// that reads such an aggregate
+int launch_sgm16(hipStream_t s, int W, int H, int D, int N, const uint16_t* vol, size_t vol_stride, int P1, int P2,
+                 int paths, uint16_t* agg, size_t agg_stride);
+int launch_quant_u16(hipStream_t s, size_t n, const float* src, uint16_t* dst);
+int launch_wta_u16(hipStream_t s, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp,
+                   float* conf);
 
 int launch_flatness(hipStream_t s, int V, int mw, int mh, const float* spixl, float gamma, float* flat);
 // labels: uint32, or uint16 when lbits == 16 (16-bit gathered maps)

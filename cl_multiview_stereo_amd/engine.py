@@ -364,6 +364,69 @@ class Engine:
                    "mvs_sgm8_batch_d")
         return out
 
+    # ---- semi-global aggregation on 16-bit integer costs (include/mvs.h at mvs_sgm8_u16_batch_d) ----
+    # The tensors are torch.uint16 (this torch build allocates it and gives its data_ptr; empty() here makes
+    # uint16); torch.int16 tensors, the same bits viewed, are accepted as well.
+    U16 = (torch.uint16, torch.int16)
+
+    def quant_u16(self, vol, out=None):
+        """float32 costs -> uint16: rint_to_even(min(max(c, 0), 2) * 2047) (mvs_quant_u16_d).  vol is
+        contiguous float32 of any shape; out has the same shape, uint16 (or int16-viewed)."""
+        if vol.dtype != torch.float32 or not vol.is_contiguous():
+            raise ValueError("quant_u16: vol must be contiguous float32")
+        out = self.empty(tuple(vol.shape), torch.uint16) if out is None else out
+        if tuple(out.shape) != tuple(vol.shape) or out.dtype not in self.U16 or not out.is_contiguous():
+            raise ValueError("quant_u16: out must be contiguous uint16 of vol's shape")
+        self._stream()
+        _lib.check(self.L.mvs_quant_u16_d(self.ctx, vol.numel(), _ptr(vol), _ptr(out)), "mvs_quant_u16_d")
+        return out
+
+    def sgm_u16_batch(self, vols, P1: int = 205, P2: int = 1638, paths: int = 15, out=None):
+        """The aggregate of N uint16 volumes of one shape in one call (mvs_sgm8_u16_batch_d): vols
+        [N, D, H, W] with costs <= 4094, integer penalties 0 <= P1 <= P2 <= 4095 (in units of 1 / 2047
+        of NCC cost), D <= 256; out[i] is the exact sum of the paths of the mask over vols[i].  The
+        layout rules are sgm_batch's, in 2-byte elements; vols and out together are
+        2 * N * 2 * D * H * W bytes."""
+        if vols.dim() != 4 or vols.dtype not in self.U16:
+            raise ValueError("sgm_u16_batch: vols must be uint16 [N, D, H, W]")
+        N, D, H, W = vols.shape
+        if N < 1:
+            raise ValueError("sgm_u16_batch: vols holds no volume")
+        if int(P1) != P1 or int(P2) != P2:
+            raise ValueError("sgm_u16_batch: the penalties are integers")
+        out = self.empty((N, D, H, W), torch.uint16) if out is None else out
+        if tuple(out.shape) != (N, D, H, W) or out.dtype not in self.U16:
+            raise ValueError("sgm_u16_batch: out must be uint16 [N, D, H, W]")
+        for t in (vols, out):
+            if not t[0].is_contiguous() or (N > 1 and t.stride(0) < D * H * W):
+                raise ValueError("sgm_u16_batch: every element must be contiguous, with stride(0) >= D * H * W")
+        self._stream()
+        # (at N = 1 a tensor's stride(0) is arbitrary and is not read)
+        vs, os_ = (D * H * W, D * H * W) if N == 1 else (vols.stride(0), out.stride(0))
+        _lib.check(self.L.mvs_sgm8_u16_batch_d(self.ctx, W, H, D, N, _ptr(vols[0]), vs, int(P1), int(P2), int(paths),
+                                               _ptr(out[0]), os_),
+                   "mvs_sgm8_u16_batch_d")
+        return out
+
+    def wta_u16(self, agg, levels: torch.Tensor, disp=None, conf=None, want_conf: bool = True):
+        """Winner (the first index of the minimum) and confidence ((c2 - best) / 2047) of a uint16
+        aggregate [D, H, W] (mvs_wta_u16_d)."""
+        if agg.dim() != 3 or agg.dtype not in self.U16:
+            raise ValueError("wta_u16: agg must be uint16 [D, H, W]")
+        D, H, W = agg.shape
+        if tuple(levels.shape) != (D,) or levels.dtype != torch.float32:
+            raise ValueError("wta_u16: levels must be float32 [D]")
+        disp = self.empty((H, W), torch.float32) if disp is None else disp
+        if want_conf and conf is None:
+            conf = self.empty((H, W), torch.float32)
+        for t in (disp, conf) if want_conf else (disp,):
+            if tuple(t.shape) != (H, W) or t.dtype != torch.float32:
+                raise ValueError("wta_u16: disp / conf must be float32 [H, W]")
+        self._stream()
+        _lib.check(self.L.mvs_wta_u16_d(self.ctx, W, H, D, _ptr(agg), _ptr(levels), _ptr(disp),
+                                        _ptr(conf) if want_conf else None), "mvs_wta_u16_d")
+        return disp, conf
+
     def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):
         """The same for reference views [z0, z1) without a volume: disp [z1 - z0, H, W] is what
         ncc_wta_range wrote; the three costs are recomputed from the window planes (bit-identical

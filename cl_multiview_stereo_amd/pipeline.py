@@ -77,11 +77,22 @@ class PixelSweep:
     group) through [min(B, V), D, H, W] buffers; every output keeps its bits.
     The two buffers take 2 * B * 4 * D * H * W bytes: 10.6 GB at 1920x1080,
     D = 128, B = 5.  With 1, the default, allocations and launches are as
-    without the option."""
+    without the option.
+    sgm_dtype="u16" (needs sgm=True and NCC cost; "f32", the default, changes
+    nothing and allocates nothing new): the aggregation runs on 16-bit integer
+    costs (include/mvs.h at mvs_sgm8_u16_batch_d).  The penalties become
+    int(round(p * 2047)) and must obey 0 <= P1 <= P2 <= 4095.  Per group of up
+    to B = sgm_batch views: ncc_volume into one reused float32 [D, H, W],
+    quant_u16 of it into q[j], one sgm_u16_batch over the group, wta_u16 of
+    agg[j] into disp_agg / conf_agg.  The buffers take
+    4 * D * H * W + 2 * B * 2 * D * H * W bytes: 6.4 GB at 1920x1080, D = 128,
+    B = 5, against 10.6 GB.  D <= 256.  disp, conf and disp_sub are as without
+    the option; disp_agg and conf_agg are those of the 16-bit definition
+    (tests/sgm16_ref.py), close to but not the float32 aggregate's."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
                  fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
-                 sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1):
+                 sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32"):
         if subpixel and cost != "ncc":
             raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
         if sgm and cost != "ncc":
@@ -90,6 +101,18 @@ class PixelSweep:
             raise ValueError("sgm_paths must be a path mask in 1..255")
         if int(sgm_batch) < 1:
             raise ValueError("sgm_batch must be at least 1")
+        if sgm_dtype not in ("f32", "u16"):
+            raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
+        if sgm_dtype == "u16" and not (sgm and cost == "ncc"):
+            raise ValueError("sgm_dtype=\"u16\" needs sgm=True and cost=\"ncc\"")
+        self.sgm_dtype = sgm_dtype
+        self.q = None
+        if sgm_dtype == "u16":
+            self.p1_u16, self.p2_u16 = int(round(sgm_p1 * 2047)), int(round(sgm_p2 * 2047))
+            if not 0 <= self.p1_u16 <= self.p2_u16 <= 4095:
+                raise ValueError("sgm_dtype=\"u16\": the penalties times 2047 must obey 0 <= P1 <= P2 <= 4095")
+            if cam.D > 256:
+                raise ValueError("sgm_dtype=\"u16\" takes at most 256 levels")
         self.e, self.cam, self.W, self.H = engine, cam, W, H
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
         self.sgm, self.sgm_p1, self.sgm_p2, self.sgm_paths = sgm, sgm_p1, sgm_p2, int(sgm_paths)
@@ -99,10 +122,15 @@ class PixelSweep:
         # views per mvs_sgm8_batch_d call (1: one mvs_sgm_d / mvs_sgm8_d call per view)
         self.sgm_batch = min(int(sgm_batch), cam.view_count) if sgm else 1
         shape = (cam.D, H, W) if self.sgm_batch == 1 else (self.sgm_batch, cam.D, H, W)
-        if cost == "ncc" and (sgm or not fused):
-            self.vol = engine.empty(shape, torch.float32)
-        if sgm:
-            self.agg = engine.empty(shape, torch.float32)
+        if sgm_dtype == "u16":  # one float32 volume, reused; the group lives in uint16
+            self.vol = engine.empty((cam.D, H, W), torch.float32)
+            self.q = engine.empty((self.sgm_batch, cam.D, H, W), torch.uint16)
+            self.agg = engine.empty((self.sgm_batch, cam.D, H, W), torch.uint16)
+        else:
+            if cost == "ncc" and (sgm or not fused):
+                self.vol = engine.empty(shape, torch.float32)
+            if sgm:
+                self.agg = engine.empty(shape, torch.float32)
         self.levels = engine.levels_dev(cam)
 
     def run(self, lab, l8, z0: int, z1: int, disp_out=None, conf_out=None, views=None):
@@ -127,7 +155,9 @@ class PixelSweep:
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
             if self.subpixel:  # the post-pass over the whole range, one call
                 self.disp_sub = self.e.ncc_sub_range(l8, box, self.cam, z0, z1, self.K, disp=disp)
-            if self.sgm_batch > 1:
+            if self.sgm_dtype == "u16":
+                self._run_groups_u16(l8, box, z0, z1, None, None)
+            elif self.sgm_batch > 1:
                 self._run_groups(l8, box, z0, z1, None, None)
             elif self.sgm:  # the volume the fused sweep never stores, for the aggregation alone
                 for i, z in enumerate(range(z0, z1)):
@@ -136,6 +166,9 @@ class PixelSweep:
             return disp, conf
         if self.subpixel:
             self.disp_sub = self.e.empty((n, self.H, self.W), torch.float32)
+        if self.sgm_dtype == "u16":
+            self._run_groups_u16(l8, box, z0, z1, disp, conf)
+            return disp, conf
         if self.sgm_batch > 1:
             self._run_groups(l8, box, z0, z1, disp, conf)
             return disp, conf
@@ -166,6 +199,26 @@ class PixelSweep:
             for j in range(g):
                 i = g0 - z0 + j
                 self.e.wta(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
+
+    def _run_groups_u16(self, l8, box, z0: int, z1: int, disp, conf):
+        """sgm_dtype="u16": _run_groups with the group in uint16.  Per view of a group ncc_volume into the one
+        float32 volume (and, in the two-pass form, wta / wta_sub of it), quant_u16 of it into q[j]; one sgm_u16_batch
+        over the group; wta_u16 of agg[j] into view i of disp_agg / conf_agg."""
+        B = self.sgm_batch
+        for g0 in range(z0, z1, B):
+            g = min(B, z1 - g0)
+            for j in range(g):
+                i = g0 - z0 + j
+                self.e.ncc_volume(l8, box, self.cam, g0 + j, self.K, out=self.vol)
+                if disp is not None:
+                    self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
+                    if self.subpixel:
+                        self.e.wta_sub(self.vol, self.levels, out=self.disp_sub[i])
+                self.e.quant_u16(self.vol, out=self.q[j])
+            self.e.sgm_u16_batch(self.q[:g], self.p1_u16, self.p2_u16, self.sgm_paths, out=self.agg[:g])
+            for j in range(g):
+                i = g0 - z0 + j
+                self.e.wta_u16(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
     def _aggregate(self, i: int):
         """self.vol -> sgm -> wta into view i of disp_agg / conf_agg."""
@@ -228,8 +281,10 @@ class Pipeline:
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
                  refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
                  subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8,
-                 sgm_paths: int = 15, sgm_batch: int = 1):
-        """sgm_batch: see PixelSweep (views aggregated per call; 2 * B * 4 * D * H * W bytes of buffers)."""
+                 sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32"):
+        """sgm_batch: see PixelSweep (views aggregated per call; 2 * B * 4 * D * H * W bytes of buffers).
+        sgm_dtype: "f32" (the default: nothing changes) or "u16", the aggregation on 16-bit integer costs, see
+        PixelSweep; its buffers are 4 * D * H * W + 2 * B * 2 * D * H * W bytes."""
         if int(sgm_batch) < 1:
             raise ValueError("sgm_batch must be at least 1")
         self.e, self.st, self.W, self.H = engine, settings, W, H
@@ -244,8 +299,12 @@ class Pipeline:
             raise ValueError("subpixel=True needs pixel_cost=\"ncc\"")
         if sgm and pixel_cost != "ncc":
             raise ValueError("sgm=True needs pixel_cost=\"ncc\"")
+        if sgm_dtype not in ("f32", "u16"):
+            raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
+        if sgm_dtype == "u16" and not (sgm and pixel_cost == "ncc"):
+            raise ValueError("sgm_dtype=\"u16\" needs sgm=True and pixel_cost=\"ncc\"")
         self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
-                                 sgm_p2, sgm_paths, sgm_batch)
+                                 sgm_p2, sgm_paths, sgm_batch, sgm_dtype)
                       if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None

@@ -274,6 +274,68 @@ int mvs_sgm8_d(mvs_ctx* ctx, int W, int H, int D, const float* vol, float P1, fl
  * axis); a stride below D*H*W; overlapping spans.  Nothing is allocated. */
 int mvs_sgm8_batch_d(mvs_ctx* ctx, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
                      int paths, float* agg, size_t agg_stride);
+/* Semi-global aggregation on 16-bit integer costs (0.9.1.1.1.1): half the bytes
+ * per cell and exact arithmetic.  Three calls: quantise a float32 cost volume,
+ * aggregate N quantised volumes, take the winner of an aggregate.  Everything is
+ * integer arithmetic except where it says otherwise.  tests/sgm16_ref.py is the
+ * definition in numpy (int64); DESIGN.md 4e has the accuracy against the float32
+ * aggregate, the kernels and the measured times. */
+#define MVS_SGM16_SCALE 2047     /* units per unit of NCC cost */
+#define MVS_SGM16_MAX_COST 4094  /* the largest quantised cost: 2 * 2047 */
+#define MVS_SGM16_MAX_P 4095     /* the largest penalty */
+/* 1. Quantise: for i < n
+ *   dst[i] = (uint16) rint_to_even( min(max(src[i], 0), 2) * 2047.0f )
+ * -- one rounded float32 multiply, then round-to-nearest-even.  src holds no NaN
+ * (as for mvs_sgm_d).  The clamp matters: mvs_ncc_volume_d returns costs down to
+ * about -0.005, and exactly 2 where there is no valid window.  n is any size
+ * (0: nothing happens); src is 4-byte and dst 2-byte aligned, nothing more is
+ * assumed; the two must not overlap.  MVS_E_ARG otherwise.  Nothing is
+ * allocated. */
+int mvs_quant_u16_d(mvs_ctx* ctx, size_t n, const float* src, uint16_t* dst);
+/* 2. Aggregate N volumes vol [D][H][W] of uint16 into agg [D][H][W] of uint16.
+ * The recurrence, the eight path bits, their directions, the first pixel of a
+ * path (L = vol there) and the treatment of the levels that do not exist are
+ * mvs_sgm8_d's, in integers:
+ *   m = min over k of L(q, k)
+ *   t = min( L(q, d), L(q, d-1) + P1 (d > 0), L(q, d+1) + P1 (d < D-1), m + P2 )
+ *   L(p, d) = vol[d][p] + t - m
+ * agg is the integer sum of L over the set bits of paths.  The sum is exact, so
+ * its order plays no part.  Whatever agg held before is overwritten.
+ * Preconditions: every vol element <= MVS_SGM16_MAX_COST (what mvs_quant_u16_d
+ * writes obeys it), and 0 <= P1 <= P2 <= MVS_SGM16_MAX_P.  Then no 16-bit value
+ * wraps: t <= m + P2, so L(p, d) <= vol[d][p] + P2 <= 4094 + 4095 = 8189, and
+ * eight paths sum to at most 8 * 8189 = 65512 < 65536.  (L >= vol[d][p] >= 0 as
+ * well: t >= m, since every member of the minimum is at least m.)  The kernels
+ * cannot check the device data: with larger vol values the result is
+ * unspecified, but every access stays inside vol and agg.
+ * Batch rules, those of mvs_sgm8_batch_d with 2-byte elements: element i
+ * (0 <= i < N) is the volume at vol + i * vol_stride, its aggregate goes to
+ * agg + i * agg_stride, and the strides count uint16 elements; element i holds
+ * bit for bit what N = 1 gives on it; nothing between the elements of agg or
+ * behind the last one is written; vol is not written; 1 <= N <= 65535; vol
+ * occupies [vol, vol + (N-1) * vol_stride + D*H*W) and agg likewise, gaps
+ * included, and the two spans must not overlap (they may abut).  vol and agg
+ * are 2-byte aligned; when they are not equal mod 16 bytes in every element
+ * (the bases differ mod 16, or with N > 1 the strides differ by no multiple of
+ * 8 elements) the horizontal paths take the slower 2-byte form.
+ * MVS_E_ARG: everything mvs_sgm8_batch_d refuses, translated to 2-byte
+ * elements; a pointer that is not 2-byte aligned; P1 < 0, P1 > P2 or P2 > 4095;
+ * paths outside 1..255.  MVS_E_UNSUPPORTED: D > 256 (the workloads use 128 and
+ * 256 levels; the kernel forms for more are left out on purpose).  Nothing is
+ * allocated. */
+int mvs_sgm8_u16_batch_d(mvs_ctx* ctx, int W, int H, int D, int N, const uint16_t* vol, size_t vol_stride, int P1,
+                         int P2, int paths, uint16_t* agg, size_t agg_stride);
+/* 3. Winner of a uint16 aggregate agg [D][H][W] (D >= 1, any D), per pixel:
+ *   b    = the FIRST index of the minimum (integer ties are common)
+ *   disp = levels[b]
+ *   c2   = the minimum of agg[k] over |k - b| > 1
+ *   conf = (float)(c2 - agg[b]) / 2047.0f  -- one correctly rounded float32
+ *          divide; 0 when no such k exists (D <= 3 cases)
+ * levels [D] and disp, conf [H][W] are float32 on the device; conf may be NULL.
+ * MVS_E_ARG: a null pointer other than conf, bad W or H, D < 1, agg not 2-byte
+ * aligned. */
+int mvs_wta_u16_d(mvs_ctx* ctx, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp,
+                  float* conf);
 /* Tuning / test hook: the NCC sweep variant this context tries first (0 =
  * automatic): waves per workgroup 4|8, levels per wave 1|2|4,
  * minimum LDS band width 64|80|96|128|192|256 columns, general_rows 1 = the kernel
