@@ -25,6 +25,7 @@ EXPORTS = [
     "mvs_wta_sub_d", "mvs_ncc_sub_range_d",
     "mvs_sgm_d", "mvs_sgm8_d", "mvs_sgm8_batch_d",
     "mvs_quant_u16_d", "mvs_sgm8_u16_batch_d", "mvs_wta_u16_d",
+    "mvs_wta_agg_sub_d", "mvs_wta_u16_sub_d",
 ]
 
 
@@ -87,6 +88,9 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                                        C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     L.mvs_wta_u16_d.restype = C.c_int
     L.mvs_wta_u16_d.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name in ("mvs_wta_agg_sub_d", "mvs_wta_u16_sub_d"):  # (ctx, W, H, D, agg, raw, levels, disp, conf, disp_sub)
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
     _lib = L
     return L
 

@@ -158,7 +158,7 @@ void* scratch(mvs_ctx* ctx, size_t bytes, int* rc) {
 extern "C" {
 
 const char* mvs_last_error(void) { return g_err.c_str(); }
-const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1.1.1 (gfx950)"; }
+const char* mvs_version(void) { return "mvs-mi355x 0.9.1.1.1.1.1 (gfx950)"; }
 
 int mvs_create(int device, mvs_ctx** out) {
   if (!out) return mvs::arg_fail("mvs_create: out is null");
@@ -437,6 +437,45 @@ int mvs_wta_u16_d(mvs_ctx* c, int W, int H, int D, const uint16_t* agg, const fl
   if (!c || !agg || !levels || !disp || D <= 0 || bad_dims(W, H) || ((uintptr_t)agg & 1))
     return mvs::arg_fail("mvs_wta_u16_d: bad arguments");
   return mvs::launch_wta_u16(c->stream, W, H, D, agg, levels, disp, conf);
+}
+
+// mvs_wta_agg_sub_d (4-byte costs) and mvs_wta_u16_sub_d (2-byte costs): one set of argument rules
+static int wta_sub_call(const char* fn, size_t esize, mvs_ctx* c, int W, int H, int D, const void* agg, const void* raw,
+                        const float* levels, float* disp, float* conf, float* disp_sub) {
+  const auto fail = [fn](const char* why) { return mvs::arg_fail((std::string(fn) + ": " + why).c_str()); };
+  if (!c || !agg || !raw || !levels || !disp_sub) return fail("null argument");
+  if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
+  if (esize == 2 && ((((uintptr_t)agg) | ((uintptr_t)raw)) & 1)) return fail("a pointer that is not 2-byte aligned");
+  typedef unsigned __int128 u128;
+  struct Span { u128 lo, hi; };
+  const u128 P = (u128)W * H;
+  const auto span = [](const void* p, u128 bytes) { return Span{(uintptr_t)p, (u128)(uintptr_t)p + bytes}; };
+  const Span in[3] = {span(agg, esize * P * D), span(raw, esize * P * D), span(levels, (u128)4 * D)};
+  Span out[3];
+  int n = 0;
+  for (const float* o : {disp, conf, disp_sub})
+    if (o) out[n++] = span(o, 4 * P);
+  for (int i = 0; i < n; i++) {
+    for (int j = 0; j < i; j++)
+      if (out[i].lo < out[j].hi && out[j].lo < out[i].hi) return fail("two outputs overlap");
+    for (const Span& s : in)
+      if (out[i].lo < s.hi && s.lo < out[i].hi) return fail("an output overlaps an input");
+  }
+  if (esize == 2)
+    return mvs::launch_wta_u16_sub(c->stream, W, H, D, (const uint16_t*)agg, (const uint16_t*)raw, levels, disp, conf,
+                                   disp_sub);
+  return mvs::launch_wta_agg_sub(c->stream, W, H, D, (const float*)agg, (const float*)raw, levels, disp, conf,
+                                 disp_sub);
+}
+
+int mvs_wta_agg_sub_d(mvs_ctx* c, int W, int H, int D, const float* agg, const float* vol, const float* levels,
+                      float* disp, float* conf, float* disp_sub) {
+  return wta_sub_call("mvs_wta_agg_sub_d", 4, c, W, H, D, agg, vol, levels, disp, conf, disp_sub);
+}
+
+int mvs_wta_u16_sub_d(mvs_ctx* c, int W, int H, int D, const uint16_t* agg, const uint16_t* raw, const float* levels,
+                      float* disp, float* conf, float* disp_sub) {
+  return wta_sub_call("mvs_wta_u16_sub_d", 2, c, W, H, D, agg, raw, levels, disp, conf, disp_sub);
 }
 
 int mvs_ncc_sub_range_d(mvs_ctx* c, int W, int H, const uint8_t* l8, const int32_t* box, const mvs_array* a, int K,

@@ -142,6 +142,12 @@ int launch_sgm16(hipStream_t s, int W, int H, int D, int N, const uint16_t* vol,
 int launch_quant_u16(hipStream_t s, size_t n, const float* src, uint16_t* dst);
 int launch_wta_u16(hipStream_t s, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp,
                    float* conf);
+// the winner of an aggregate with the sub-level fit through the raw costs at that winner (include/mvs.h at
+// mvs_wta_agg_sub_d: wta.hip; at mvs_wta_u16_sub_d: sgm16.hip); disp and conf may each be null
+int launch_wta_agg_sub(hipStream_t s, int W, int H, int D, const float* agg, const float* vol, const float* levels,
+                       float* disp, float* conf, float* disp_sub);
+int launch_wta_u16_sub(hipStream_t s, int W, int H, int D, const uint16_t* agg, const uint16_t* raw,
+                       const float* levels, float* disp, float* conf, float* disp_sub);
 
 int launch_flatness(hipStream_t s, int V, int mw, int mh, const float* spixl, float gamma, float* flat);
 // labels: uint32, or uint16 when lbits == 16 (16-bit gathered maps)

@@ -37,9 +37,11 @@
 // Every form takes the batch on blockIdx.y.  Plane bases are 64-bit, offsets within a plane 32-bit.
 //
 // k_quant_u16 and k_wta_u16 are the streaming passes before and behind: float32 costs -> uint16, and the winner
-// with its confidence from a uint16 aggregate.
+// with its confidence from a uint16 aggregate.  k_wta_u16_sub is that winner pass with the sub-level fit through the
+// raw (quantised, not aggregated) costs at the winner.
 #include "mvs_internal.h"
 #include "wave.h"
+#include "wta_common.h"
 
 namespace mvs {
 namespace {
@@ -447,6 +449,86 @@ __global__ __launch_bounds__(256) void k_wta_u16(const uint16_t* __restrict__ ag
   for (int k = 0; k < NP; k++) t[k].emit(levels, disp, conf, p + k);
 }
 
+// ---- winner of a uint16 aggregate + the fit through the raw costs at that winner ----------------
+// (include/mvs.h at mvs_wta_u16_sub_d).  k_wta_u16's pass over agg, read once, in both of its forms; then every
+// pixel gathers three raw costs and three levels from planes b-1, b, b+1.  The plane indices are clamped into
+// [0, D) before the loads (b at an end: the index, not a branch), so every address lies inside raw and levels and
+// no lane-dependent condition stands between an address and its load; the one select sits behind all of a lane's
+// loads.  raw goes by 2-byte loads in the four-pixel form as well: its alignment is its own.
+template <int NP, int UNR>
+__global__ __launch_bounds__(256) void k_wta_u16_sub(const uint16_t* __restrict__ agg, const uint16_t* __restrict__ raw,
+                                                     const float* __restrict__ levels, long P, int D,
+                                                     float* __restrict__ disp, float* __restrict__ conf,
+                                                     float* __restrict__ sub) {
+  typedef unsigned short vec __attribute__((ext_vector_type(NP)));
+  const long p = (blockIdx.x * (long)blockDim.x + threadIdx.x) * NP;
+  if (p >= P) return;
+  Top4u t[NP];
+  int dl = 0;
+  if constexpr (NP == 1) {
+    const uint16_t* col = agg + p;
+    for (; dl + UNR <= D; dl += UNR) {
+      int c[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; u++) c[u] = (int)__builtin_nontemporal_load(col + (long)(dl + u) * P);
+#pragma unroll
+      for (int u = 0; u < UNR; u++) t[0].insert(c[u], dl + u);
+    }
+    for (; dl < D; dl++) t[0].insert((int)col[(long)dl * P], dl);
+  } else {
+    const vec* col = (const vec*)(agg + p);
+    const long Pv = P / NP;
+    for (; dl + UNR <= D; dl += UNR) {
+      vec c[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; u++) c[u] = __builtin_nontemporal_load(col + (long)(dl + u) * Pv);
+#pragma unroll
+      for (int u = 0; u < UNR; u++)
+#pragma unroll
+        for (int k = 0; k < NP; k++) t[k].insert((int)c[u][k], dl + u);
+    }
+    for (; dl < D; dl++) {
+      const vec c = col[(long)dl * Pv];
+#pragma unroll
+      for (int k = 0; k < NP; k++) t[k].insert((int)c[k], dl);
+    }
+  }
+  // conf first: from here on only the winners' indices stay live beside the gathered values
+  if (conf) {
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      const Top4u& q = t[k];
+      const int c2 = second_cost(q.i0, q.i1, q.v1, q.i2, q.v2, q.i3, q.v3, -1);
+      conf[p + k] = c2 < 0 ? 0.0f : (float)(c2 - q.v0) / 2047.0f;
+    }
+  }
+  int b[NP], rm[NP], r0[NP], rp[NP];
+  float lm[NP], lb[NP], lp[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) {  // (D >= 1 and every cost is below kInf: i0 >= 0; the clamp keeps that off the address)
+    b[k] = min(max(t[k].i0, 0), D - 1);
+    const int bm = max(b[k] - 1, 0), bp = min(b[k] + 1, D - 1);
+    const uint16_t* rc = raw + p + k;
+    rm[k] = (int)rc[(long)bm * P];
+    r0[k] = (int)rc[(long)b[k] * P];
+    rp[k] = (int)rc[(long)bp * P];
+    lm[k] = levels[bm];
+    lb[k] = levels[b[k]];
+    lp[k] = levels[bp];
+  }
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    if (disp) disp[p + k] = lb[k];
+    // both sides measured (4094: no valid window) and raw has its minimum at b (mvs_wta_d's tie rule): den >= 1
+    const bool ok = b[k] > 0 && b[k] < D - 1 && rm[k] < 4094 && rp[k] < 4094 && rm[k] > r0[k] && rp[k] >= r0[k];
+    const int den = (rm[k] - r0[k]) + (rp[k] - r0[k]);
+    const float off = (float)(rm[k] - rp[k]) / (float)(2 * den);
+    const float step = off < 0.0f ? lb[k] - lm[k] : lp[k] - lb[k];
+    const float prod = off * step;
+    sub[p + k] = ok ? lb[k] + prod : lb[k];
+  }
+}
+
 }  // namespace
 
 int launch_sgm16(hipStream_t s, int W, int H, int D, int N, const uint16_t* vol, size_t vol_stride, int P1, int P2,
@@ -536,6 +618,20 @@ int launch_wta_u16(hipStream_t s, int W, int H, int D, const uint16_t* agg, cons
     hipLaunchKernelGGL((k_wta_u16<1, 16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, agg, levels, P, D, disp,
                        conf);
   MVS_LAUNCH_CHECK("k_wta_u16");
+  return 0;
+}
+
+int launch_wta_u16_sub(hipStream_t s, int W, int H, int D, const uint16_t* agg, const uint16_t* raw,
+                       const float* levels, float* disp, float* conf, float* disp_sub) {
+  const long P = (long)W * H;
+  // launch_wta_u16's choice, from agg alone
+  if (P % 4 == 0 && ((uintptr_t)agg & 7) == 0)
+    hipLaunchKernelGGL((k_wta_u16_sub<4, 8>), dim3((unsigned)((P / 4 + 255) / 256)), dim3(256), 0, s, agg, raw, levels,
+                       P, D, disp, conf, disp_sub);
+  else
+    hipLaunchKernelGGL((k_wta_u16_sub<1, 16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, agg, raw, levels, P,
+                       D, disp, conf, disp_sub);
+  MVS_LAUNCH_CHECK("k_wta_u16_sub");
   return 0;
 }
 

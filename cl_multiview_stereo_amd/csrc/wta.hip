@@ -4,7 +4,9 @@
 //                    (the HBM-streaming pass the roofline is quoted on); the fused
 //                    sweeps (ncc.hip, ncc_mfma.hip) fold the same from kWtaInit
 //  k_wta_sub         winner-take-all + the sub-level parabola fit (definition: ncc_sub.hip)
+//  k_wta_agg_sub     k_wta over an aggregate + the fit through the raw volume's costs at the aggregate's winner
 #include "ncc_common.h"
+#include "wta_common.h"
 
 namespace mvs {
 namespace {
@@ -91,6 +93,46 @@ __global__ __launch_bounds__(256) void k_wta_sub(const float* __restrict__ vol, 
   out[p] = r;
 }
 
+// ---- winner of an aggregate + the fit through the raw costs at that winner ---------------
+// (include/mvs.h at mvs_wta_agg_sub_d).  k_wta<1, UNR>'s pass over agg, read once, with its Top4 and its disp and
+// conf; then three raw costs and three levels are gathered from planes b-1, b, b+1.  The three plane indices
+// are clamped into [0, D) before the loads, so every address lies inside vol and levels for every lane, b at an
+// end and "no winner" (i0 < 0) included, and no lane-dependent condition stands between an address and its load;
+// what must not count is dropped by the one select behind all six loads.  vol is addressed on its own: nothing
+// of agg's alignment is assumed for it.
+template <int UNR>
+__global__ __launch_bounds__(256) void k_wta_agg_sub(const float* __restrict__ agg, const float* __restrict__ vol,
+                                                     const float* __restrict__ levels, long P, int D,
+                                                     float* __restrict__ disp, float* __restrict__ conf,
+                                                     float* __restrict__ sub) {
+  const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  Top4 t;
+  const float* col = agg + p;
+  int dl = 0;
+  for (; dl + UNR <= D; dl += UNR) {
+    float c[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; u++) c[u] = __builtin_nontemporal_load(col + (long)(dl + u) * P);
+#pragma unroll
+    for (int u = 0; u < UNR; u++) t.insert(c[u], dl + u);
+  }
+  for (; dl < D; dl++) t.insert(col[(long)dl * P], dl);
+  const int b = max(t.i0, 0), bm = max(b - 1, 0), bp = min(b + 1, D - 1);
+  const float* rc = vol + p;
+  const float cm = rc[(long)bm * P], c0 = rc[(long)b * P], cp = rc[(long)bp * P];
+  const float lm = levels[bm], lb = levels[b], lp = levels[bp];
+  if (disp) disp[p] = t.i0 >= 0 ? lb : 0.0f;
+  if (conf) {
+    const float c2 = second_cost(t.i0, t.i1, t.v1, t.i2, t.v2, t.i3, t.v3, kWtaInit);
+    conf[p] = (t.i0 < 0 || c2 == kWtaInit) ? 0.0f : c2 - t.v0;
+  }
+  // raw has its minimum at b (mvs_wta_d's tie rule): den > 0, |off| <= 0.5
+  const bool ok = b > 0 && b < D - 1 && cm > c0 && cp >= c0;
+  const float fit = parabola(cm, c0, cp, lm, lb, lp);
+  sub[p] = t.i0 < 0 ? 0.0f : ok ? fit : lb;
+}
+
 }  // namespace
 
 int launch_wta(hipStream_t s, int W, int H, int D, const float* vol, const float* levels, float* disp,
@@ -108,6 +150,16 @@ int launch_wta_sub(hipStream_t s, int W, int H, int D, const float* vol, const f
   const long P = (long)W * H;
   hipLaunchKernelGGL(k_wta_sub, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, vol, levels, P, D, disp_sub);
   MVS_LAUNCH_CHECK("k_wta_sub");
+  return 0;
+}
+
+int launch_wta_agg_sub(hipStream_t s, int W, int H, int D, const float* agg, const float* vol, const float* levels,
+                       float* disp, float* conf, float* disp_sub) {
+  const long P = (long)W * H;
+  // launch_wta's form: one pixel per lane, 16 levels in flight
+  hipLaunchKernelGGL(k_wta_agg_sub<16>, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, agg, vol, levels, P, D,
+                     disp, conf, disp_sub);
+  MVS_LAUNCH_CHECK("k_wta_agg_sub");
   return 0;
 }
 

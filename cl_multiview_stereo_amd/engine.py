@@ -427,6 +427,44 @@ class Engine:
                                         _ptr(conf) if want_conf else None), "mvs_wta_u16_d")
         return disp, conf
 
+    def _wta_sub_call(self, name, what, agg, raw, levels, disp, conf, out, want_conf):
+        D, H, W = agg.shape
+        if tuple(raw.shape) != (D, H, W) or raw.dtype != agg.dtype:
+            raise ValueError(f"{what}: the raw volume must have agg's shape and dtype")
+        if tuple(levels.shape) != (D,) or levels.dtype != torch.float32:
+            raise ValueError(f"{what}: levels must be float32 [D]")
+        out = self.empty((H, W), torch.float32) if out is None else out
+        if want_conf and conf is None:
+            conf = self.empty((H, W), torch.float32)
+        if not want_conf:
+            conf = None
+        for t in (disp, conf, out):
+            if t is not None and (tuple(t.shape) != (H, W) or t.dtype != torch.float32):
+                raise ValueError(f"{what}: disp / conf / out must be float32 [H, W]")
+        self._stream()
+        _lib.check(getattr(self.L, name)(self.ctx, W, H, D, _ptr(agg), _ptr(raw), _ptr(levels), _ptr(disp), _ptr(conf),
+                                         _ptr(out)), name)
+        return disp, conf, out
+
+    def wta_agg_sub(self, agg, vol, levels: torch.Tensor, disp=None, conf=None, out=None, want_conf: bool = True):
+        """Winner of a float32 aggregate [D, H, W] with the sub-level disparity of that winner: the parabola
+        through the costs of the raw volume vol [D, H, W] at the aggregate's winner and its two neighbours, where
+        vol has a minimum there (mvs_wta_agg_sub_d).  agg is read once.  Returns (disp, conf, out): out [H, W] is
+        the sub-level disparity; disp is written only where a tensor is given (else None), conf unless
+        want_conf is False; both hold wta(agg)'s bits."""
+        if agg.dim() != 3 or agg.dtype != torch.float32:
+            raise ValueError("wta_agg_sub: agg must be float32 [D, H, W]")
+        return self._wta_sub_call("mvs_wta_agg_sub_d", "wta_agg_sub", agg, vol, levels, disp, conf, out, want_conf)
+
+    def wta_u16_sub(self, agg, raw, levels: torch.Tensor, disp=None, conf=None, out=None, want_conf: bool = True):
+        """wta_agg_sub for a uint16 aggregate and the quantised volume raw it was aggregated from
+        (mvs_wta_u16_sub_d): disp and conf hold wta_u16(agg)'s bits."""
+        if agg.dim() != 3 or agg.dtype not in self.U16 or raw.dtype not in self.U16:
+            raise ValueError("wta_u16_sub: agg and raw must be uint16 [D, H, W]")
+        if raw.dtype != agg.dtype:
+            raw = raw.view(agg.dtype)
+        return self._wta_sub_call("mvs_wta_u16_sub_d", "wta_u16_sub", agg, raw, levels, disp, conf, out, want_conf)
+
     def ncc_sub_range(self, l8, box, cam: CameraArray, z0: int, z1: int, K: int = 5, disp=None, out=None):
         """The same for reference views [z0, z1) without a volume: disp [z1 - z0, H, W] is what
         ncc_wta_range wrote; the three costs are recomputed from the window planes (bit-identical

@@ -88,11 +88,21 @@ class PixelSweep:
     4 * D * H * W + 2 * B * 2 * D * H * W bytes: 6.4 GB at 1920x1080, D = 128,
     B = 5, against 10.6 GB.  D <= 256.  disp, conf and disp_sub are as without
     the option; disp_agg and conf_agg are those of the 16-bit definition
-    (tests/sgm16_ref.py), close to but not the float32 aggregate's."""
+    (tests/sgm16_ref.py), close to but not the float32 aggregate's.
+    sgm_subpixel=True (needs sgm=True; independent of subpixel; False, the
+    default, changes nothing): run() also leaves self.disp_agg_sub
+    [z1 - z0, H, W] beside disp_agg and conf_agg, the sub-level disparity of
+    the aggregate's winner: the parabola through the raw volume's costs at
+    that winner (include/mvs.h at mvs_wta_agg_sub_d; tests/sgm_sub_ref.py).
+    In each of the three aggregation paths the winner pass over agg becomes
+    wta_agg_sub(agg, vol) or wta_u16_sub(agg[j], q[j]): agg is still read
+    once, no buffer is added besides the output, every other output keeps
+    its bits."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
                  fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
-                 sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32"):
+                 sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32",
+                 sgm_subpixel: bool = False):
         if subpixel and cost != "ncc":
             raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
         if sgm and cost != "ncc":
@@ -105,7 +115,9 @@ class PixelSweep:
             raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
         if sgm_dtype == "u16" and not (sgm and cost == "ncc"):
             raise ValueError("sgm_dtype=\"u16\" needs sgm=True and cost=\"ncc\"")
-        self.sgm_dtype = sgm_dtype
+        if sgm_subpixel and not sgm:
+            raise ValueError("sgm_subpixel=True needs sgm=True: it is the sub-level disparity of the aggregate's winner")
+        self.sgm_dtype, self.sgm_subpixel = sgm_dtype, bool(sgm_subpixel)
         self.q = None
         if sgm_dtype == "u16":
             self.p1_u16, self.p2_u16 = int(round(sgm_p1 * 2047)), int(round(sgm_p2 * 2047))
@@ -117,7 +129,7 @@ class PixelSweep:
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
         self.sgm, self.sgm_p1, self.sgm_p2, self.sgm_paths = sgm, sgm_p1, sgm_p2, int(sgm_paths)
         self.disp_sub = None
-        self.disp_agg = self.conf_agg = None
+        self.disp_agg = self.conf_agg = self.disp_agg_sub = None
         self.vol = self.agg = None
         # views per mvs_sgm8_batch_d call (1: one mvs_sgm_d / mvs_sgm8_d call per view)
         self.sgm_batch = min(int(sgm_batch), cam.view_count) if sgm else 1
@@ -151,6 +163,8 @@ class PixelSweep:
         if self.sgm:
             self.disp_agg = self.e.empty((n, self.H, self.W), torch.float32)
             self.conf_agg = self.e.empty((n, self.H, self.W), torch.float32)
+            if self.sgm_subpixel:
+                self.disp_agg_sub = self.e.empty((n, self.H, self.W), torch.float32)
         if self.fused:  # every reference view of the call, runs of views per launch
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
             if self.subpixel:  # the post-pass over the whole range, one call
@@ -184,7 +198,7 @@ class PixelSweep:
     def _run_groups(self, l8, box, z0: int, z1: int, disp, conf):
         """sgm_batch > 1: the views of [z0, z1) in groups of at most sgm_batch (the last may be shorter).  Per view
         of a group ncc_volume into vol[j] (and, in the two-pass form, where disp is given, wta / wta_sub of it), one
-        sgm_batch over the group, then wta of agg[j] into view i of disp_agg / conf_agg."""
+        sgm_batch over the group, then the winner pass (_winner) of agg[j] into view i of disp_agg / conf_agg."""
         B = self.sgm_batch
         for g0 in range(z0, z1, B):
             g = min(B, z1 - g0)
@@ -198,12 +212,13 @@ class PixelSweep:
             self.e.sgm_batch(self.vol[:g], self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg[:g])
             for j in range(g):
                 i = g0 - z0 + j
-                self.e.wta(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
+                self._winner(self.agg[j], self.vol[j], i)
 
     def _run_groups_u16(self, l8, box, z0: int, z1: int, disp, conf):
         """sgm_dtype="u16": _run_groups with the group in uint16.  Per view of a group ncc_volume into the one
         float32 volume (and, in the two-pass form, wta / wta_sub of it), quant_u16 of it into q[j]; one sgm_u16_batch
-        over the group; wta_u16 of agg[j] into view i of disp_agg / conf_agg."""
+        over the group; wta_u16 of agg[j] (with sgm_subpixel wta_u16_sub of agg[j] and q[j]) into view i of disp_agg /
+        conf_agg."""
         B = self.sgm_batch
         for g0 in range(z0, z1, B):
             g = min(B, z1 - g0)
@@ -218,12 +233,25 @@ class PixelSweep:
             self.e.sgm_u16_batch(self.q[:g], self.p1_u16, self.p2_u16, self.sgm_paths, out=self.agg[:g])
             for j in range(g):
                 i = g0 - z0 + j
-                self.e.wta_u16(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
+                if self.sgm_subpixel:
+                    self.e.wta_u16_sub(self.agg[j], self.q[j], self.levels, disp=self.disp_agg[i],
+                                       conf=self.conf_agg[i], out=self.disp_agg_sub[i])
+                else:
+                    self.e.wta_u16(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
     def _aggregate(self, i: int):
-        """self.vol -> sgm -> wta into view i of disp_agg / conf_agg."""
+        """self.vol -> sgm -> the winner pass into view i of disp_agg / conf_agg."""
         self.e.sgm(self.vol, self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg)
-        self.e.wta(self.agg, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
+        self._winner(self.agg, self.vol, i)
+
+    def _winner(self, agg, vol, i: int):
+        """The float32 aggregate's winner pass into view i: wta, or with sgm_subpixel wta_agg_sub, which also fits
+        through vol at that winner."""
+        if self.sgm_subpixel:
+            self.e.wta_agg_sub(agg, vol, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i],
+                               out=self.disp_agg_sub[i])
+        else:
+            self.e.wta(agg, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
 
 class DepthRefinement:
@@ -257,6 +285,7 @@ class StepOutput:
     disp_sub: torch.Tensor | None = None  # sub-level disparity (Pipeline(subpixel=True)), else None
     disp_agg: torch.Tensor | None = None  # winner of the semi-globally aggregated volume (Pipeline(sgm=True)), else None
     conf_agg: torch.Tensor | None = None  # its confidence
+    disp_agg_sub: torch.Tensor | None = None  # its sub-level disparity (Pipeline(sgm_subpixel=True)), else None
     disp_refined: torch.Tensor | None = None
     disp_filtered: torch.Tensor | None = None
 
@@ -281,10 +310,12 @@ class Pipeline:
                  view_subset: list[list[int]] | None = None, pixel_cost: str | None = "ncc",
                  refine: bool = False, filt: bool = False, concurrent: bool = False, fused: bool = False,
                  subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1, sgm_p2: float = 0.8,
-                 sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32"):
+                 sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32", sgm_subpixel: bool = False):
         """sgm_batch: see PixelSweep (views aggregated per call; 2 * B * 4 * D * H * W bytes of buffers).
         sgm_dtype: "f32" (the default: nothing changes) or "u16", the aggregation on 16-bit integer costs, see
-        PixelSweep; its buffers are 4 * D * H * W + 2 * B * 2 * D * H * W bytes."""
+        PixelSweep; its buffers are 4 * D * H * W + 2 * B * 2 * D * H * W bytes.
+        sgm_subpixel: with sgm=True, the result also carries disp_agg_sub, the sub-level disparity of the aggregate's
+        winner (see PixelSweep)."""
         if int(sgm_batch) < 1:
             raise ValueError("sgm_batch must be at least 1")
         self.e, self.st, self.W, self.H = engine, settings, W, H
@@ -303,8 +334,10 @@ class Pipeline:
             raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
         if sgm_dtype == "u16" and not (sgm and pixel_cost == "ncc"):
             raise ValueError("sgm_dtype=\"u16\" needs sgm=True and pixel_cost=\"ncc\"")
+        if sgm_subpixel and not sgm:
+            raise ValueError("sgm_subpixel=True needs sgm=True")
         self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
-                                 sgm_p2, sgm_paths, sgm_batch, sgm_dtype)
+                                 sgm_p2, sgm_paths, sgm_batch, sgm_dtype, sgm_subpixel)
                       if pixel_cost else None)
         self.refiner = DepthRefinement(engine, self.cam, settings.spixl_size) if refine else None
         self.filter = ConsistencyFilter(engine, settings.array_width, settings.bl_ratio, settings.fuse) if filt else None
@@ -344,6 +377,7 @@ class Pipeline:
             out.disp_sub = self.pixel.disp_sub
         if self.pixel is not None and self.pixel.sgm:
             out.disp_agg, out.conf_agg = self.pixel.disp_agg, self.pixel.conf_agg
+            out.disp_agg_sub = self.pixel.disp_agg_sub
         if self.refiner is not None:
             r = self.refiner.do_refinement(spixl, labels, rep, self.st)
             out.disp_refined = r["disp"]

@@ -227,7 +227,8 @@ int mvs_ncc_sub_range_d(mvs_ctx* ctx, int W, int H, const uint8_t* l8, const int
  * mvs_wta_d on agg gives the aggregated disparity and confidence.
  * mvs_wta_sub_d on agg is NOT defined: its ok rule reads a cost of 2 as "no
  * measurement", which does not carry over to sums; take the sub-level
- * disparity from the raw volume.
+ * disparity from the raw volume.  mvs_wta_agg_sub_d and mvs_wta_u16_sub_d
+ * (below, 0.9.1.1.1.1.1) do that at the aggregate's winner.
  * MVS_E_ARG: a null pointer, bad W or H, D < 1 or D > 16384, paths outside
  * 1..15, a penalty that is not finite, negative, or P1 > P2, agg == vol (the
  * two must not overlap at all).  Nothing is allocated. */
@@ -336,6 +337,44 @@ int mvs_sgm8_u16_batch_d(mvs_ctx* ctx, int W, int H, int D, int N, const uint16_
  * aligned. */
 int mvs_wta_u16_d(mvs_ctx* ctx, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp,
                   float* conf);
+/* Sub-level disparity of a semi-global aggregate (0.9.1.1.1.1.1): the winner is
+ * the aggregate's, the parabola goes through the RAW costs of the same view at
+ * that winner and its two index neighbours.  (A fit through the aggregated
+ * costs is biased: the +P1 branch of the recurrence caps the aggregate beside
+ * the winner, which flattens the parabola; DESIGN.md 4f has both measured.)
+ * tests/sgm_sub_ref.py is the definition in numpy.  agg and raw (vol) are
+ * [D][H][W] of one shape, levels [D] float32 on the device, need not be
+ * ordered.  Per pixel, uint16 form (mvs_wta_u16_sub_d):
+ *   b    = first index of the minimum of agg                 (mvs_wta_u16_d's rule)
+ *   rm, r0, rp = raw[b-1], raw[b], raw[b+1]                   (integers)
+ *   ok   = 0 < b < D-1  and  rm < 4094  and  rp < 4094        (MVS_SGM16_MAX_COST: no valid window)
+ *          and  rm > r0  and  rp >= r0                        (raw has a minimum at b, mvs_wta_d's tie rule)
+ *   den  = (rm - r0) + (rp - r0)                              (integer, 1 .. 8186 when ok)
+ *   off  = (float)(rm - rp) / (float)(2 * den)                (one correctly rounded float32 divide;
+ *                                                              |off| <= 0.5; +0.5 iff rp == r0)
+ *   step = off < 0 ? levels[b] - levels[b-1] : levels[b+1] - levels[b]
+ *   disp_sub = ok ? levels[b] + off * step : levels[b]        (product rounded, then the sum; no fused multiply-add)
+ * float32 form (mvs_wta_agg_sub_d): b by mvs_wta_d's rule on agg; cm, c0, cp =
+ * vol[b-1], vol[b], vol[b+1]; ok = 0 < b < D-1 and cm < 2 and cp < 2 and
+ * cm > c0 and cp >= c0; from there mvs_wta_sub_d's arithmetic: den =
+ * (cm - c0) + (cp - c0), off = (0.5 * (cm - cp)) / den, step and disp_sub as
+ * above.  With agg and vol holding the same values the result is
+ * mvs_wta_sub_d's, bit for bit.  agg and vol hold no NaN; where no agg cost is
+ * below 1e6 (mvs_wta_d writes disp 0 and conf 0 there) disp_sub is 0.
+ * Without "raw has a minimum at b" nothing would keep den above 0 at a winner
+ * the aggregation moved; such a pixel keeps levels[b], as does one whose side
+ * has no valid window (on those a fit through the aggregate measured no gain).
+ * disp and conf may each be NULL; where given they hold bit for bit what
+ * mvs_wta_d(agg) / mvs_wta_u16_d(agg) writes.  disp_sub is required.  agg is
+ * read once.  agg and vol / raw are read only and may overlap or be one buffer;
+ * the three outputs [H][W] must overlap neither each other nor an input.
+ * MVS_E_ARG: a null pointer other than disp or conf, bad W or H, D < 1, a uint16
+ * pointer that is not 2-byte aligned, overlapping outputs.  Any D.  Nothing is
+ * allocated. */
+int mvs_wta_agg_sub_d(mvs_ctx* ctx, int W, int H, int D, const float* agg, const float* vol, const float* levels,
+                      float* disp, float* conf, float* disp_sub);
+int mvs_wta_u16_sub_d(mvs_ctx* ctx, int W, int H, int D, const uint16_t* agg, const uint16_t* raw, const float* levels,
+                      float* disp, float* conf, float* disp_sub);
 /* Tuning / test hook: the NCC sweep variant this context tries first (0 =
  * automatic): waves per workgroup 4|8, levels per wave 1|2|4,
  * minimum LDS band width 64|80|96|128|192|256 columns, general_rows 1 = the kernel
