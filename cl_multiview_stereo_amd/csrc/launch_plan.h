@@ -203,11 +203,11 @@ struct FilterPlan {
 FilterPlan plan_remove_incons(const Tuning& t, int V, int W, int H, int aw, int z0, int z1, int ya, int yb,
                               bool band);
 
-// ---- launch_sgm (sgm.hip) ---------------------------------------------------
+// ---- launch_sgm (sgm.hip; the kernels: sgm_kernels.h, on cost type C) -------
 // One path of the semi-global aggregation (include/mvs.h at mvs_sgm_d) over a
 // volume [D][H][W].  path: 0 left->right, 1 right->left (lines = rows, n = W
 // steps), 2 top->bottom, 3 bottom->top (lines = columns, n = H steps).
-//  * kSgmLanes, k_sgm_lanes<lpl, vec, waves > 1>: one workgroup of `waves`
+//  * kSgmLanes, k_sgm_lanes<C, lpl, vec, waves > 1>: one workgroup of `waves`
 //    waves per line, every lane keeps lpl consecutive levels of the previous
 //    pixel in registers and walks the line; element i of line l of a level's
 //    plane is at l * lstride + i * sstride.  vec: the line is contiguous
@@ -253,7 +253,7 @@ SgmPlan plan_sgm(int W, int H, int D, int path);
 //    there iff that lies in [0, W).  The workgroup walks the rows
 //    [sgm_diag_ylo, sgm_diag_yhi], the rows at which some lane is live, in the
 //    path's order; levels over the waves as in the columns form.
-//  * kSgmLanes, k_sgm_lanes<lpl, false, waves > 1, true> above: one workgroup
+//  * kSgmLanes, k_sgm_lanes<C, lpl, false, waves > 1, true> above: one workgroup
 //    per line; sgm_diag_line gives the line's topmost pixel and its length,
 //    and its elements are sstride = W + sx apart.
 constexpr int kSgmSheared = 2;
@@ -306,13 +306,34 @@ struct SgmBatchPlan {
   unsigned grid_y = 0;
   bool vec_ok = false;
 };
+// The 16-byte pieces of k_sgm_lanes, for both cost types: a piece holds `piece` pixels of 16 / piece bytes (4
+// floats, 8 uint16; a power of two).
+//  * sgm_piece_vec_ok: vol and agg are equal mod 16 bytes in every element of the batch (strides in elements).
+//  * sgm_piece_phase: for a (lane, level) whose line starts at byte address a, pixel x is element
+//    j = sgm_piece_elem = (x + ph) mod piece, ph = (a / element size) mod piece, of the piece of pixels
+//    x - j .. x - j + piece - 1, which starts at a multiple of 16 bytes.
+//  * sgm_piece_inside: that piece lies inside the line of n pixels (it is then read and written whole; else its
+//    pixels are handled one by one).
+// tests/host/sgm16_plan_check.cpp checks them against brute force at both piece sizes.
+constexpr bool sgm_piece_vec_ok(int piece, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
+                                size_t agg_stride) {
+  return ((vol_addr ^ agg_addr) & 15) == 0 && (N == 1 || ((vol_stride - agg_stride) & (size_t)(piece - 1)) == 0);
+}
+constexpr int sgm_piece_phase(int piece, uintptr_t line_addr) {
+  return (int)((line_addr / (uintptr_t)(16 / piece)) & (uintptr_t)(piece - 1));
+}
+constexpr int sgm_piece_elem(int piece, int ph, int x) { return (x + ph) & (piece - 1); }
+constexpr bool sgm_piece_inside(int piece, int ph, int x, int n) {
+  return x - sgm_piece_elem(piece, ph, x) >= 0 && x - sgm_piece_elem(piece, ph, x) + piece - 1 < n;
+}
+constexpr int kSgmPiece = 4;  // float32 pixels per 16-byte piece
 constexpr bool sgm_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
-  return ((vol_addr ^ agg_addr) & 15) == 0 && (N == 1 || ((vol_stride - agg_stride) & 3) == 0);
+  return sgm_piece_vec_ok(kSgmPiece, N, vol_addr, vol_stride, agg_addr, agg_stride);
 }
 SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
                             size_t agg_stride);
 
-// ---- launch_sgm16 (sgm16.hip) -----------------------------------------------
+// ---- launch_sgm16 (sgm16.hip; sgm_kernels.h on uint16 costs) ----------------
 // The same aggregation on 16-bit integer costs (include/mvs.h at mvs_sgm8_u16_batch_d).  The geometry of a path is
 // plan_sgm's and plan_sgm_diag's as they are (D <= kSgm16MaxD: the lanes form with 1, 2 or 4 levels per lane and
 // one wave for the horizontal paths, the columns form for the vertical ones, the sheared form for the diagonal
@@ -321,10 +342,7 @@ SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size
 //    no multiple of 2 refused.  unsupported (with err set): D > kSgm16MaxD.
 //  * vec_ok: the 16-byte-pieces form needs vol and agg equal mod 16 bytes in every element: the bases are, and
 //    with N > 1 the strides differ by a multiple of 8 elements.  Else the whole batch takes the 2-byte form.
-//  * sgm16_phase: a piece holds eight pixels.  For a (lane, level) whose line starts at byte address a, pixel x
-//    is element j = (x + ph) mod 8, ph = (a / 2) mod 8, of the piece of pixels x - j .. x - j + 7, which starts
-//    at a multiple of 16 bytes; sgm16_piece_inside says whether that piece lies inside the line of n pixels (it
-//    is then read and written whole; else its pixels are handled one by one).
+//  * sgm16_phase, sgm16_piece_elem, sgm16_piece_inside: the piece arithmetic above at eight pixels per piece.
 constexpr int kSgm16MaxD = kSgmColumnsMaxD;  // 256 levels: the forms for more are left out
 constexpr int kSgm16MaxCost = 4094, kSgm16MaxP = 4095;
 constexpr int kSgm16Piece = 8;  // pixels per 16-byte piece
@@ -335,13 +353,11 @@ struct Sgm16BatchPlan {
   bool vec_ok = false;
 };
 constexpr bool sgm16_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
-  return ((vol_addr ^ agg_addr) & 15) == 0 && (N == 1 || ((vol_stride - agg_stride) & 7) == 0);
+  return sgm_piece_vec_ok(kSgm16Piece, N, vol_addr, vol_stride, agg_addr, agg_stride);
 }
-constexpr int sgm16_phase(uintptr_t line_addr) { return (int)((line_addr >> 1) & 7); }
-constexpr int sgm16_piece_elem(int ph, int x) { return (x + ph) & 7; }
-constexpr bool sgm16_piece_inside(int ph, int x, int n) {
-  return x - sgm16_piece_elem(ph, x) >= 0 && x - sgm16_piece_elem(ph, x) + 7 < n;
-}
+constexpr int sgm16_phase(uintptr_t line_addr) { return sgm_piece_phase(kSgm16Piece, line_addr); }
+constexpr int sgm16_piece_elem(int ph, int x) { return sgm_piece_elem(kSgm16Piece, ph, x); }
+constexpr bool sgm16_piece_inside(int ph, int x, int n) { return sgm_piece_inside(kSgm16Piece, ph, x, n); }
 Sgm16BatchPlan plan_sgm16_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
                                 size_t agg_stride);
 

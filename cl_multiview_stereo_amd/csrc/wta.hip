@@ -13,62 +13,26 @@ namespace {
 using namespace ncc;
 
 // ---- winner-take-all + confidence ----------------------------------------
-// the 4 smallest (cost, level) of one pixel in lexicographic order
-struct Top4 {
-  float v0 = kWtaInit, v1 = kWtaInit, v2 = kWtaInit, v3 = kWtaInit;
-  int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
-  __device__ __forceinline__ void insert(float cc, int ci) {
-    if (cc < v3) {
-      if (cc < v2) {
-        v3 = v2; i3 = i2;
-        if (cc < v1) {
-          v2 = v1; i2 = i1;
-          if (cc < v0) { v1 = v0; i1 = i0; v0 = cc; i0 = ci; }
-          else { v1 = cc; i1 = ci; }
-        } else { v2 = cc; i2 = ci; }
-      } else { v3 = cc; i3 = ci; }
-    }
-  }
-  __device__ __forceinline__ void emit(const float* levels, float* disp, float* conf, long p) const {
-    disp[p] = i0 >= 0 ? levels[i0] : 0.0f;
-    if (conf) {
-      float c2 = kWtaInit;
-      if (i1 >= 0 && (i1 < i0 - 1 || i1 > i0 + 1)) c2 = v1;
-      else if (i2 >= 0 && (i2 < i0 - 1 || i2 > i0 + 1)) c2 = v2;
-      else if (i3 >= 0 && (i3 < i0 - 1 || i3 > i0 + 1)) c2 = v3;
-      conf[p] = (i0 < 0 || c2 == kWtaInit) ? 0.0f : c2 - v0;
-    }
-  }
-};
+// c2 - c0 of the winner c0 and the smallest cost c2 outside its neighbour levels; 0 where either is missing
+__device__ __forceinline__ float confidence(const Top4<float>& t) {
+  const float c2 = t.second(kWtaInit);
+  return (t.i0 < 0 || c2 == kWtaInit) ? 0.0f : c2 - t.v0;
+}
 
 // One lane per NP consecutive pixels (NP-wide non-temporal vector loads, so a
 // wave streams 256 NP contiguous bytes per level), UNR levels in flight.
 template <int NP, int UNR>
 __global__ __launch_bounds__(256) void k_wta(const float* __restrict__ vol, const float* __restrict__ levels, long P,
                                              int D, float* __restrict__ disp, float* __restrict__ conf) {
-  typedef float vec __attribute__((ext_vector_type(NP)));
   const long p = (blockIdx.x * (long)blockDim.x + threadIdx.x) * NP;
   if (p >= P) return;
-  Top4 t[NP];
-  const vec* col = (const vec*)(vol + p);
-  const long Pv = P / NP;
-  int dl = 0;
-  for (; dl + UNR <= D; dl += UNR) {
-    vec c[UNR];
+  Top4<float> t[NP];
+  MVS_SCAN_TOP4(NP, UNR, float, float, vol + p, P, D, kWtaInit, t);
 #pragma unroll
-    for (int u = 0; u < UNR; u++) c[u] = __builtin_nontemporal_load(col + (long)(dl + u) * Pv);
-#pragma unroll
-    for (int u = 0; u < UNR; u++)
-#pragma unroll
-      for (int k = 0; k < NP; k++) t[k].insert(c[u][k], dl + u);
+  for (int k = 0; k < NP; k++) {
+    disp[p + k] = t[k].i0 >= 0 ? levels[t[k].i0] : 0.0f;
+    if (conf) conf[p + k] = confidence(t[k]);
   }
-  for (; dl < D; dl++) {
-    const vec c = col[(long)dl * Pv];
-#pragma unroll
-    for (int k = 0; k < NP; k++) t[k].insert(c[k], dl);
-  }
-#pragma unroll
-  for (int k = 0; k < NP; k++) t[k].emit(levels, disp, conf, p + k);
 }
 
 // ---- winner-take-all + sub-level fit (b and parabola: ncc_sub.hip's header) -
@@ -94,7 +58,7 @@ __global__ __launch_bounds__(256) void k_wta_sub(const float* __restrict__ vol, 
 }
 
 // ---- winner of an aggregate + the fit through the raw costs at that winner ---------------
-// (include/mvs.h at mvs_wta_agg_sub_d).  k_wta<1, UNR>'s pass over agg, read once, with its Top4 and its disp and
+// (include/mvs.h at mvs_wta_agg_sub_d).  k_wta<1, UNR>'s pass over agg, read once, with its Top4, its disp and its
 // conf; then three raw costs and three levels are gathered from planes b-1, b, b+1.  The three plane indices
 // are clamped into [0, D) before the loads, so every address lies inside vol and levels for every lane, b at an
 // end and "no winner" (i0 < 0) included, and no lane-dependent condition stands between an address and its load;
@@ -107,26 +71,15 @@ __global__ __launch_bounds__(256) void k_wta_agg_sub(const float* __restrict__ a
                                                      float* __restrict__ sub) {
   const long p = blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (p >= P) return;
-  Top4 t;
-  const float* col = agg + p;
-  int dl = 0;
-  for (; dl + UNR <= D; dl += UNR) {
-    float c[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; u++) c[u] = __builtin_nontemporal_load(col + (long)(dl + u) * P);
-#pragma unroll
-    for (int u = 0; u < UNR; u++) t.insert(c[u], dl + u);
-  }
-  for (; dl < D; dl++) t.insert(col[(long)dl * P], dl);
+  Top4<float> t1[1];
+  MVS_SCAN_TOP4(1, UNR, float, float, agg + p, P, D, kWtaInit, t1);
+  const Top4<float>& t = t1[0];
   const int b = max(t.i0, 0), bm = max(b - 1, 0), bp = min(b + 1, D - 1);
   const float* rc = vol + p;
   const float cm = rc[(long)bm * P], c0 = rc[(long)b * P], cp = rc[(long)bp * P];
   const float lm = levels[bm], lb = levels[b], lp = levels[bp];
   if (disp) disp[p] = t.i0 >= 0 ? lb : 0.0f;
-  if (conf) {
-    const float c2 = second_cost(t.i0, t.i1, t.v1, t.i2, t.v2, t.i3, t.v3, kWtaInit);
-    conf[p] = (t.i0 < 0 || c2 == kWtaInit) ? 0.0f : c2 - t.v0;
-  }
+  if (conf) conf[p] = confidence(t);
   // raw has its minimum at b (mvs_wta_d's tie rule): den > 0, |off| <= 0.5
   const bool ok = b > 0 && b < D - 1 && cm > c0 && cp >= c0;
   const float fit = parabola(cm, c0, cp, lm, lb, lp);

@@ -10,8 +10,10 @@
 //     pixel x, the piece of pixel x starts at a multiple of 16 bytes, holds x at element sgm16_piece_elem, and
 //     sgm16_piece_inside equals "all eight pixels of that piece lie in [0, n)"; the pieces inside a line are
 //     disjoint and every pixel is either in exactly one of them or handled singly.
+//  5. The same for the general piece arithmetic (sgm_piece_phase, sgm_piece_elem, sgm_piece_inside) at both piece
+//     sizes, 4 float32 and 8 uint16 pixels, and sgm_piece_vec_ok against its two instances.
 // Links only the planner; built with the address and undefined-behaviour sanitizers (Makefile: plancheck).
-// Prints one line per case.  Exit status 0: every check held.
+// Prints one line per case of 1 to 4.  Exit status 0: every check held.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -159,6 +161,45 @@ int main() {
       }
     }
     CHECK(whole > 0 && single > 0);
+  }
+  // 5. the general piece arithmetic: 4's assertions, the piece size a variable
+  for (const int piece : {kSgmPiece, kSgm16Piece}) {
+    const int elem = 16 / piece;  // bytes per pixel
+    int whole = 0, single = 0;
+    for (uint64_t a = 4096; a < 4096 + 16; a += elem) {
+      const int ph = sgm_piece_phase(piece, (uintptr_t)a);
+      CHECK(ph == (int)((a / elem) % piece));
+      if (piece == kSgm16Piece) CHECK(ph == sgm16_phase((uintptr_t)a));
+      for (int n = 1; n <= 40; n++) {
+        int owner[40];
+        for (int x = 0; x < n; x++) {
+          const int j = sgm_piece_elem(piece, ph, x), xs = x - j;
+          CHECK(j >= 0 && j < piece);
+          CHECK(((int64_t)a + elem * (int64_t)xs) % 16 == 0);
+          const bool inside = xs >= 0 && xs + piece - 1 < n;
+          CHECK(sgm_piece_inside(piece, ph, x, n) == inside);
+          if (piece == kSgm16Piece) CHECK(j == sgm16_piece_elem(ph, x) && inside == sgm16_piece_inside(ph, x, n));
+          owner[x] = inside ? xs : -1;
+          (inside ? whole : single)++;
+        }
+        for (int x = 0; x < n; x++) {
+          if (owner[x] >= 0) {
+            for (int k = 0; k < piece; k++) CHECK(owner[owner[x] + k] == owner[x]);
+          } else {
+            CHECK(x < piece - 1 || x > n - piece);
+          }
+        }
+      }
+    }
+    CHECK(whole > 0 && single > 0);
+    for (int N : {1, 2})
+      for (uint64_t da = 0; da < 16; da += elem)
+        for (uint64_t ds = 0; ds < 9; ds++) {
+          const bool ok = sgm_piece_vec_ok(piece, N, 4096, 1000 + ds, 8192 + da, 1000);
+          CHECK(ok == (da == 0 && (N == 1 || ds % piece == 0)));
+          CHECK(ok == (piece == kSgmPiece ? sgm_batch_vec_ok(N, 4096, 1000 + ds, 8192 + da, 1000)
+                                          : sgm16_batch_vec_ok(N, 4096, 1000 + ds, 8192 + da, 1000)));
+        }
   }
   if (g_bad) std::printf("%d checks failed\n", g_bad);
   return g_bad ? 1 : 0;
