@@ -368,40 +368,55 @@ int mvs_wta_sub_d(mvs_ctx* c, int W, int H, int D, const float* vol, const float
   return mvs::launch_wta_sub(c->stream, W, H, D, vol, levels, disp_sub);
 }
 
-// mvs_sgm_d (masks to 15), mvs_sgm8_d (to 255) and mvs_sgm8_batch_d (batch: N volumes, strides and the span rule of
-// plan_sgm_batch): one set of argument rules, the message names the entry point
-static int sgm_call(const char* fn, int max_paths, mvs_ctx* c, int W, int H, int D, const float* vol, float P1,
-                    float P2, int paths, float* agg, bool batch = false, int N = 1, size_t vol_stride = 0,
-                    size_t agg_stride = 0) {
+// mvs_sgm_d (masks to 15), mvs_sgm8_d (to 255), mvs_sgm8_batch_d and mvs_sgm8_u16_batch_d (batch: N volumes, strides
+// and the rules of plan_sgm_batch for the cost type): one set of argument rules, the message names the entry point.
+// The penalty rule of a cost type, as its message:
+extern "C++" {  // (overloads and a template)
+static const char* bad_penalties(float P1, float P2) {  // (a NaN fails every comparison)
+  return !(P1 >= 0.0f) || !(P2 >= P1) || !(P2 <= 3.402823466e38f) ? "penalties must be finite with 0 <= P1 <= P2"
+                                                                  : nullptr;
+}
+static const char* bad_penalties(int P1, int P2) {
+  return P1 < 0 || P2 < P1 || P2 > mvs::plan::kSgm16MaxP ? "penalties must obey 0 <= P1 <= P2 <= 4095" : nullptr;
+}
+template <class T, class P>
+static int sgm_call(const char* fn, mvs::plan::SgmCost cost,
+                    int (*launch)(hipStream_t, int, int, int, int, const T*, size_t, P, P, int, T*, size_t),
+                    int max_paths, mvs_ctx* c, int W, int H, int D, const T* vol, P P1, P P2, int paths, T* agg,
+                    bool batch = false, int N = 1, size_t vol_stride = 0, size_t agg_stride = 0) {
   const auto fail = [fn](const std::string& why) { return mvs::arg_fail((std::string(fn) + ": " + why).c_str()); };
   if (!c || !vol || !agg) return fail("null argument");
   if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
-  if (D > mvs::plan::kSgmMaxD) return fail("more than 16384 levels");
+  // (a cost type whose larger forms are merely not built says so through the plan, below)
+  if (!cost.unsupported && D > cost.max_d) return fail("more than " + std::to_string(cost.max_d) + " levels");
   if (paths < 1 || paths > max_paths) return fail("paths must be a mask in 1.." + std::to_string(max_paths));
-  // (a NaN fails every comparison)
-  if (!(P1 >= 0.0f) || !(P2 >= P1) || !(P2 <= 3.402823466e38f))
-    return fail("penalties must be finite with 0 <= P1 <= P2");
+  if (const char* why = bad_penalties(P1, P2)) return fail(why);
   if (batch) {
     const mvs::plan::SgmBatchPlan b =
-        mvs::plan::plan_sgm_batch(W, H, D, N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
-    if (b.err) return fail(b.err);
+        mvs::plan::plan_sgm_batch(cost, W, H, D, N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
+    if (b.err) {
+      fail(b.err);
+      return b.unsupported ? MVS_E_UNSUPPORTED : MVS_E_ARG;
+    }
   } else if (agg == vol) {
     return fail("agg must not be vol");
   }
-  return mvs::launch_sgm(c->stream, W, H, D, N, vol, vol_stride, P1, P2, paths, agg, agg_stride);
+  return launch(c->stream, W, H, D, N, vol, vol_stride, P1, P2, paths, agg, agg_stride);
 }
+}  // extern "C++"
 
 int mvs_sgm_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
-  return sgm_call("mvs_sgm_d", 15, c, W, H, D, vol, P1, P2, paths, agg);
+  return sgm_call("mvs_sgm_d", mvs::plan::kSgmF32, mvs::launch_sgm, 15, c, W, H, D, vol, P1, P2, paths, agg);
 }
 
 int mvs_sgm8_d(mvs_ctx* c, int W, int H, int D, const float* vol, float P1, float P2, int paths, float* agg) {
-  return sgm_call("mvs_sgm8_d", 255, c, W, H, D, vol, P1, P2, paths, agg);
+  return sgm_call("mvs_sgm8_d", mvs::plan::kSgmF32, mvs::launch_sgm, 255, c, W, H, D, vol, P1, P2, paths, agg);
 }
 
 int mvs_sgm8_batch_d(mvs_ctx* c, int W, int H, int D, int N, const float* vol, size_t vol_stride, float P1, float P2,
                      int paths, float* agg, size_t agg_stride) {
-  return sgm_call("mvs_sgm8_batch_d", 255, c, W, H, D, vol, P1, P2, paths, agg, true, N, vol_stride, agg_stride);
+  return sgm_call("mvs_sgm8_batch_d", mvs::plan::kSgmF32, mvs::launch_sgm, 255, c, W, H, D, vol, P1, P2, paths, agg,
+                  true, N, vol_stride, agg_stride);
 }
 
 // the 16-bit aggregation: float32 costs -> uint16, the aggregate of N uint16 volumes, its winner
@@ -419,18 +434,8 @@ int mvs_quant_u16_d(mvs_ctx* c, size_t n, const float* src, uint16_t* dst) {
 
 int mvs_sgm8_u16_batch_d(mvs_ctx* c, int W, int H, int D, int N, const uint16_t* vol, size_t vol_stride, int P1, int P2,
                          int paths, uint16_t* agg, size_t agg_stride) {
-  const auto fail = [](const std::string& why) { return mvs::arg_fail(("mvs_sgm8_u16_batch_d: " + why).c_str()); };
-  if (!c || !vol || !agg) return fail("null argument");
-  if (bad_dims(W, H) || D < 1) return fail("bad dimensions");
-  if (paths < 1 || paths > 255) return fail("paths must be a mask in 1..255");
-  if (P1 < 0 || P2 < P1 || P2 > mvs::plan::kSgm16MaxP) return fail("penalties must obey 0 <= P1 <= P2 <= 4095");
-  const mvs::plan::Sgm16BatchPlan b =
-      mvs::plan::plan_sgm16_batch(W, H, D, N, (uintptr_t)vol, vol_stride, (uintptr_t)agg, agg_stride);
-  if (b.err) {
-    fail(b.err);
-    return b.unsupported ? MVS_E_UNSUPPORTED : MVS_E_ARG;
-  }
-  return mvs::launch_sgm16(c->stream, W, H, D, N, vol, vol_stride, P1, P2, paths, agg, agg_stride);
+  return sgm_call("mvs_sgm8_u16_batch_d", mvs::plan::kSgmU16, mvs::launch_sgm16, 255, c, W, H, D, vol, P1, P2, paths,
+                  agg, true, N, vol_stride, agg_stride);
 }
 
 int mvs_wta_u16_d(mvs_ctx* c, int W, int H, int D, const uint16_t* agg, const float* levels, float* disp, float* conf) {

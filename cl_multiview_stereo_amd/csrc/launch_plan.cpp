@@ -415,8 +415,8 @@ SgmPlan plan_sgm(int W, int H, int D, int path) {
   return p;
 }
 
-SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path) {
-  SgmDiagPlan p;
+SgmPlan plan_sgm_diag(int W, int H, int D, int path) {
+  SgmPlan p;
   if (W < 1 || H < 1 || D < 1 || path < 4 || path > 7) {
     p.err = "sgm: bad dimensions or path";
     return p;
@@ -428,6 +428,7 @@ SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path) {
   p.sx = path < 6 ? 1 : -1;
   p.rev = path & 1;
   p.lines = W + H - 1;
+  p.n = W, p.lstride = H;  // (what k_sgm_lanes at DIAG takes in these places)
   p.sstride = W + p.sx;
   if (D <= kSgmColumnsMaxD) {
     p.form = kSgmSheared;
@@ -450,15 +451,25 @@ SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path) {
   return p;
 }
 
-SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
-                            size_t agg_stride) {
+SgmBatchPlan plan_sgm_batch(SgmCost cost, int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride,
+                            uintptr_t agg_addr, size_t agg_stride) {
   SgmBatchPlan p;
-  if (W < 1 || H < 1 || D < 1 || D > kSgmMaxD || (long)W * H > (1L << 27)) {
+  const unsigned esize = 16u / (unsigned)cost.piece;
+  if (W < 1 || H < 1 || D < 1 || (long)W * H > (1L << 27)) {
     p.err = "bad dimensions";
+    return p;
+  }
+  if (D > cost.max_d) {
+    p.err = cost.unsupported ? "more than 256 levels: the 16-bit forms are not built for them" : "bad dimensions";
+    p.unsupported = cost.unsupported;
     return p;
   }
   if (N < 1 || N > kSgmMaxBatch) {
     p.err = "N must be in 1..65535";
+    return p;
+  }
+  if (esize == 2 && ((vol_addr | agg_addr) & 1)) {
+    p.err = "a pointer that is not 2-byte aligned";
     return p;
   }
   const size_t dhw = (size_t)D * (size_t)H * (size_t)W;  // <= 2^41
@@ -468,52 +479,14 @@ SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size
   }
   // the spans in bytes; 128 bits: a stride is any size_t
   typedef unsigned __int128 u128;
-  const u128 v0 = vol_addr, v1 = v0 + 4 * ((u128)(N - 1) * vol_stride + dhw);
-  const u128 a0 = agg_addr, a1 = a0 + 4 * ((u128)(N - 1) * agg_stride + dhw);
+  const u128 v0 = vol_addr, v1 = v0 + esize * ((u128)(N - 1) * vol_stride + dhw);
+  const u128 a0 = agg_addr, a1 = a0 + esize * ((u128)(N - 1) * agg_stride + dhw);
   if (v0 < a1 && a0 < v1) {
     p.err = "the vol and agg spans overlap";
     return p;
   }
   p.grid_y = (unsigned)N;
-  p.vec_ok = sgm_batch_vec_ok(N, vol_addr, vol_stride, agg_addr, agg_stride);
-  return p;
-}
-
-Sgm16BatchPlan plan_sgm16_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
-                                size_t agg_stride) {
-  Sgm16BatchPlan p;
-  if (W < 1 || H < 1 || D < 1 || (long)W * H > (1L << 27)) {
-    p.err = "bad dimensions";
-    return p;
-  }
-  if (D > kSgm16MaxD) {
-    p.err = "more than 256 levels: the 16-bit forms are not built for them";
-    p.unsupported = true;
-    return p;
-  }
-  if (N < 1 || N > kSgmMaxBatch) {
-    p.err = "N must be in 1..65535";
-    return p;
-  }
-  if ((vol_addr | agg_addr) & 1) {
-    p.err = "a pointer that is not 2-byte aligned";
-    return p;
-  }
-  const size_t dhw = (size_t)D * (size_t)H * (size_t)W;  // <= 2^35
-  if (vol_stride < dhw || agg_stride < dhw) {
-    p.err = "a stride below D*H*W";
-    return p;
-  }
-  // the spans in bytes; 128 bits: a stride is any size_t
-  typedef unsigned __int128 u128;
-  const u128 v0 = vol_addr, v1 = v0 + 2 * ((u128)(N - 1) * vol_stride + dhw);
-  const u128 a0 = agg_addr, a1 = a0 + 2 * ((u128)(N - 1) * agg_stride + dhw);
-  if (v0 < a1 && a0 < v1) {
-    p.err = "the vol and agg spans overlap";
-    return p;
-  }
-  p.grid_y = (unsigned)N;
-  p.vec_ok = sgm16_batch_vec_ok(N, vol_addr, vol_stride, agg_addr, agg_stride);
+  p.vec_ok = sgm_piece_vec_ok(cost.piece, N, vol_addr, vol_stride, agg_addr, agg_stride);
   return p;
 }
 

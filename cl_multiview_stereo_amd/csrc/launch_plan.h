@@ -236,7 +236,8 @@ struct SgmPlan {
   bool vec = false;    // lanes form: 16-byte pieces
   int n = 0, lines = 0;  // steps of a path; rows or columns
   int sstride = 0, lstride = 0;
-  bool rev = false;    // walk from the line's last element down
+  int sx = 0;          // plan_sgm_diag: the column's step per image row
+  bool rev = false;    // walk from the line's last element (sheared form: the last row) down
   unsigned grid = 0, block = 0;
   size_t lds = 0;      // static LDS of the kernel form, bytes
 };
@@ -256,6 +257,8 @@ SgmPlan plan_sgm(int W, int H, int D, int path);
 //  * kSgmLanes, k_sgm_lanes<C, lpl, false, waves > 1, true> above: one workgroup
 //    per line; sgm_diag_line gives the line's topmost pixel and its length,
 //    and its elements are sstride = W + sx apart.
+// The plan is an SgmPlan as the launcher passes it on: lines = W + H - 1, and W and H travel in the places of n
+// and lstride (k_sgm_lanes at DIAG takes them there); lpl counts levels per wave in the sheared form.
 constexpr int kSgmSheared = 2;
 constexpr int sgm_diag_x0(int g, int lane, int H, int sx) { return sx > 0 ? 64 * g - (H - 1) + lane : 64 * g + lane; }
 constexpr int sgm_diag_ylo(int g, int W, int H, int sx) {
@@ -277,37 +280,42 @@ constexpr SgmDiagLine sgm_diag_line(int W, int H, int sx, int l) {
   const int nx = sx > 0 ? W - xt : xt + 1, ny = H - yt;
   return {yt * W + xt, nx < ny ? nx : ny};
 }
-struct SgmDiagPlan {
-  const char* err = nullptr;  // the argument error, if any
-  int form = kSgmSheared;
-  int sx = 0;          // the column's step per image row
-  bool rev = false;    // walk from the last row (sheared) or the line's last element (lanes) down
-  int lpl = 1;         // levels per wave (sheared form) or per lane (lanes form)
-  int waves = 1;       // per workgroup
-  int lines = 0;       // W + H - 1
-  int sstride = 0;     // lanes form: W + sx
-  unsigned grid = 0, block = 0;
-  size_t lds = 0;      // static LDS of the kernel form, bytes
-};
-SgmDiagPlan plan_sgm_diag(int W, int H, int D, int path);
+SgmPlan plan_sgm_diag(int W, int H, int D, int path);
 
-// N volumes of one shape per launch (include/mvs.h at mvs_sgm8_batch_d): element i is the volume at
-// vol + i * vol_stride and its aggregate at agg + i * agg_stride (addresses in bytes, strides in floats).  The
-// batch index is the grid's second axis, so every launch of plan_sgm / plan_sgm_diag becomes (grid, grid_y).
-//  * err: N outside 1..kSgmMaxBatch, a stride below D H W, or the two spans
-//    [addr, addr + 4 ((N - 1) stride + D H W)) overlap (abutting spans do not); also bad dimensions.
+// N volumes of one shape per launch (include/mvs.h at mvs_sgm8_batch_d and mvs_sgm8_u16_batch_d): element i is the
+// volume at vol + i * vol_stride and its aggregate at agg + i * agg_stride (addresses in bytes, strides in
+// elements).  The batch index is the grid's second axis, so every launch of plan_sgm / plan_sgm_diag becomes
+// (grid, grid_y).  An SgmCost holds what the cost type sets: float32, or the 16-bit integer costs of sgm16.hip,
+// whose paths have plan_sgm's and plan_sgm_diag's geometry as it is (D <= kSgm16MaxD: the lanes form with 1, 2 or
+// 4 levels per lane and one wave for the horizontal paths, the columns form for the vertical ones, the sheared
+// form for the diagonal ones).  The rules, in this order:
+//  * err: bad dimensions; more than max_d levels (with `unsupported` set where the cost type says so: the forms
+//    for more are left out, not impossible); N outside 1..kSgmMaxBatch; for 2-byte elements an address that is no
+//    multiple of 2; a stride below D H W; the two spans
+//    [addr, addr + element size * ((N - 1) stride + D H W)) overlap (abutting spans do not).
 //  * vec_ok: the 16-byte-pieces form of k_sgm_lanes needs vol and agg equal mod 16 bytes in every element: the
-//    bases are, and with N > 1 the strides differ by a multiple of 4 floats.  (The strides themselves need be
-//    no multiple of 4: a (lane, level)'s phase comes from its real address.)  Else the whole batch takes the
-//    scalar form.
+//    bases are, and with N > 1 the strides differ by a multiple of `piece` elements.  (The strides themselves need
+//    be no multiple of it: a (lane, level)'s phase comes from its real address.)  Else the whole batch takes the
+//    element-wise form.
 constexpr int kSgmMaxBatch = 65535;  // one grid axis
+constexpr int kSgm16MaxD = kSgmColumnsMaxD;  // 256 levels: the forms for more are left out
+constexpr int kSgm16MaxCost = 4094, kSgm16MaxP = 4095;
+constexpr int kSgmPiece = 4, kSgm16Piece = 8;  // float32, uint16 pixels per 16-byte piece
+struct SgmCost {
+  int piece;         // pixels per 16-byte piece (a power of two): an element has 16 / piece bytes
+  int max_d;         // the level limit
+  bool unsupported;  // more levels are "unsupported", not bad dimensions
+};
+constexpr SgmCost kSgmF32 = {kSgmPiece, kSgmMaxD, false}, kSgmU16 = {kSgm16Piece, kSgm16MaxD, true};
 struct SgmBatchPlan {
   const char* err = nullptr;  // the argument error, if any
+  bool unsupported = false;   // err is "more levels than the forms built take"
   unsigned grid_y = 0;
   bool vec_ok = false;
 };
-// The 16-byte pieces of k_sgm_lanes, for both cost types: a piece holds `piece` pixels of 16 / piece bytes (4
-// floats, 8 uint16; a power of two).
+SgmBatchPlan plan_sgm_batch(SgmCost cost, int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride,
+                            uintptr_t agg_addr, size_t agg_stride);
+// The 16-byte pieces of k_sgm_lanes, for both cost types: a piece holds `piece` pixels of 16 / piece bytes.
 //  * sgm_piece_vec_ok: vol and agg are equal mod 16 bytes in every element of the batch (strides in elements).
 //  * sgm_piece_phase: for a (lane, level) whose line starts at byte address a, pixel x is element
 //    j = sgm_piece_elem = (x + ph) mod piece, ph = (a / element size) mod piece, of the piece of pixels
@@ -326,40 +334,6 @@ constexpr int sgm_piece_elem(int piece, int ph, int x) { return (x + ph) & (piec
 constexpr bool sgm_piece_inside(int piece, int ph, int x, int n) {
   return x - sgm_piece_elem(piece, ph, x) >= 0 && x - sgm_piece_elem(piece, ph, x) + piece - 1 < n;
 }
-constexpr int kSgmPiece = 4;  // float32 pixels per 16-byte piece
-constexpr bool sgm_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
-  return sgm_piece_vec_ok(kSgmPiece, N, vol_addr, vol_stride, agg_addr, agg_stride);
-}
-SgmBatchPlan plan_sgm_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
-                            size_t agg_stride);
-
-// ---- launch_sgm16 (sgm16.hip; sgm_kernels.h on uint16 costs) ----------------
-// The same aggregation on 16-bit integer costs (include/mvs.h at mvs_sgm8_u16_batch_d).  The geometry of a path is
-// plan_sgm's and plan_sgm_diag's as they are (D <= kSgm16MaxD: the lanes form with 1, 2 or 4 levels per lane and
-// one wave for the horizontal paths, the columns form for the vertical ones, the sheared form for the diagonal
-// ones); what differs is counted in 2-byte elements:
-//  * err: as plan_sgm_batch, with the spans [addr, addr + 2 ((N - 1) stride + D H W)) and an address that is
-//    no multiple of 2 refused.  unsupported (with err set): D > kSgm16MaxD.
-//  * vec_ok: the 16-byte-pieces form needs vol and agg equal mod 16 bytes in every element: the bases are, and
-//    with N > 1 the strides differ by a multiple of 8 elements.  Else the whole batch takes the 2-byte form.
-//  * sgm16_phase, sgm16_piece_elem, sgm16_piece_inside: the piece arithmetic above at eight pixels per piece.
-constexpr int kSgm16MaxD = kSgmColumnsMaxD;  // 256 levels: the forms for more are left out
-constexpr int kSgm16MaxCost = 4094, kSgm16MaxP = 4095;
-constexpr int kSgm16Piece = 8;  // pixels per 16-byte piece
-struct Sgm16BatchPlan {
-  const char* err = nullptr;  // the argument error, if any
-  bool unsupported = false;   // err is "more levels than the 16-bit forms take"
-  unsigned grid_y = 0;
-  bool vec_ok = false;
-};
-constexpr bool sgm16_batch_vec_ok(int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr, size_t agg_stride) {
-  return sgm_piece_vec_ok(kSgm16Piece, N, vol_addr, vol_stride, agg_addr, agg_stride);
-}
-constexpr int sgm16_phase(uintptr_t line_addr) { return sgm_piece_phase(kSgm16Piece, line_addr); }
-constexpr int sgm16_piece_elem(int ph, int x) { return sgm_piece_elem(kSgm16Piece, ph, x); }
-constexpr bool sgm16_piece_inside(int ph, int x, int n) { return sgm_piece_inside(kSgm16Piece, ph, x, n); }
-Sgm16BatchPlan plan_sgm16_batch(int W, int H, int D, int N, uintptr_t vol_addr, size_t vol_stride, uintptr_t agg_addr,
-                                size_t agg_stride);
 
 }  // namespace plan
 }  // namespace mvs

@@ -472,15 +472,7 @@ int launch_sgm_paths(hipStream_t s, int W, int H, int D, int N, const typename C
   for (int path = 0; path < 8; path++) {
     if (!((paths >> path) & 1)) continue;
     const bool diag = path >= 4;
-    plan::SgmPlan p;
-    int sx = 0;
-    if (!diag) {
-      p = plan::plan_sgm(W, H, D, path);
-    } else {  // as a plan of lines: W and H travel in the places of n and lstride (k_sgm_lanes at DIAG)
-      const plan::SgmDiagPlan q = plan::plan_sgm_diag(W, H, D, path);
-      p.err = q.err, p.form = q.form, p.lpl = q.lpl, p.waves = q.waves, p.rev = q.rev, p.grid = q.grid;
-      p.block = q.block, p.n = W, p.sstride = q.sstride, p.lstride = H, sx = q.sx;
-    }
+    const plan::SgmPlan p = diag ? plan::plan_sgm_diag(W, H, D, path) : plan::plan_sgm(W, H, D, path);
     if (p.err) return arg_fail(p.err);
     const dim3 grid(p.grid, (unsigned)N), block(p.block);
     const int rev = (int)p.rev;
@@ -500,11 +492,11 @@ int launch_sgm_paths(hipStream_t s, int W, int H, int D, int N, const typename C
                            P1, P2);
     } else if (p.form == plan::kSgmSheared) {
       if (p.block <= 512)
-        hipLaunchKernelGGL((k_sgm_diag<C, 512>), grid, block, 0, s, vol, agg, vstride, astride, D, W, H, sx, rev, acc,
+        hipLaunchKernelGGL((k_sgm_diag<C, 512>), grid, block, 0, s, vol, agg, vstride, astride, D, W, H, p.sx, rev, acc,
                            P1, P2);
       else
-        hipLaunchKernelGGL((k_sgm_diag<C, 1024>), grid, block, 0, s, vol, agg, vstride, astride, D, W, H, sx, rev, acc,
-                           P1, P2);
+        hipLaunchKernelGGL((k_sgm_diag<C, 1024>), grid, block, 0, s, vol, agg, vstride, astride, D, W, H, p.sx, rev,
+                           acc, P1, P2);
     } else if constexpr (!ABOVE256) {  // D <= 256: one wave, 1, 2 or 4 levels per lane, contiguous lines
       if (diag || p.waves != 1 || p.lpl > 4 || p.sstride != 1) return arg_fail(refused);
       if (p.vec && vec_ok) {

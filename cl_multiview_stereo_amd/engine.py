@@ -302,15 +302,19 @@ class Engine:
             self._levels_dev[key] = t
         return t
 
-    def wta(self, vol, levels: torch.Tensor, disp=None, conf=None, want_conf: bool = True):
+    def _wta_call(self, name, vol, levels, disp, conf, want_conf):
+        """wta and wta_u16: the winner pass `name` over vol [D, H, W]."""
         D, H, W = vol.shape
         disp = self.empty((H, W), torch.float32) if disp is None else disp
         if want_conf and conf is None:
             conf = self.empty((H, W), torch.float32)
         self._stream()
-        _lib.check(self.L.mvs_wta_d(self.ctx, W, H, D, _ptr(vol), _ptr(levels), _ptr(disp),
-                                    _ptr(conf) if want_conf else None), "mvs_wta_d")
+        _lib.check(getattr(self.L, name)(self.ctx, W, H, D, _ptr(vol), _ptr(levels), _ptr(disp),
+                                         _ptr(conf) if want_conf else None), name)
         return disp, conf
+
+    def wta(self, vol, levels: torch.Tensor, disp=None, conf=None, want_conf: bool = True):
+        return self._wta_call("mvs_wta_d", vol, levels, disp, conf, want_conf)
 
     def wta_sub(self, vol, levels: torch.Tensor, out=None):
         """Sub-level disparity over a materialised volume [D, H, W]: the parabola fit through
@@ -339,30 +343,35 @@ class Engine:
                                          _ptr(out)), name)
         return out
 
+    def _sgm_batch_call(self, name, what, dtypes, tname, vols, P1, P2, paths, out):
+        """sgm_batch and sgm_u16_batch: the entry point `name` on vols and out of a dtype in dtypes (tname in the
+        messages; an out made here has dtypes[0]), with the penalties as the entry point takes them."""
+        if vols.dim() != 4 or vols.dtype not in dtypes:
+            raise ValueError(f"{what}: vols must be {tname} [N, D, H, W]")
+        N, D, H, W = vols.shape
+        if N < 1:
+            raise ValueError(f"{what}: vols holds no volume")
+        out = self.empty((N, D, H, W), dtypes[0]) if out is None else out
+        if tuple(out.shape) != (N, D, H, W) or out.dtype not in dtypes:
+            raise ValueError(f"{what}: out must be {tname} [N, D, H, W]")
+        for t in (vols, out):
+            if not t[0].is_contiguous() or (N > 1 and t.stride(0) < D * H * W):
+                raise ValueError(f"{what}: every element must be contiguous, with stride(0) >= D * H * W")
+        self._stream()
+        # (at N = 1 a tensor's stride(0) is arbitrary and is not read)
+        vs, os_ = (D * H * W, D * H * W) if N == 1 else (vols.stride(0), out.stride(0))
+        _lib.check(getattr(self.L, name)(self.ctx, W, H, D, N, _ptr(vols[0]), vs, P1, P2, int(paths), _ptr(out[0]),
+                                         os_), name)
+        return out
+
     def sgm_batch(self, vols, P1: float = 0.1, P2: float = 0.8, paths: int = 15, out=None):
         """sgm of N volumes of one shape in one call (include/mvs.h at mvs_sgm8_batch_d): vols
         float32 [N, D, H, W], one launch per path over all N; out[i] holds the bits sgm(vols[i])
         gives.  Each vols[i] is contiguous and stride(0) >= D * H * W (a view into a padded buffer
         is allowed); out obeys the same rule and must not overlap vols, gaps included.  vols and
         out together are 2 * N * 4 * D * H * W bytes."""
-        if vols.dim() != 4 or vols.dtype != torch.float32:
-            raise ValueError("sgm_batch: vols must be float32 [N, D, H, W]")
-        N, D, H, W = vols.shape
-        if N < 1:
-            raise ValueError("sgm_batch: vols holds no volume")
-        out = self.empty((N, D, H, W), torch.float32) if out is None else out
-        if tuple(out.shape) != (N, D, H, W) or out.dtype != torch.float32:
-            raise ValueError("sgm_batch: out must be float32 [N, D, H, W]")
-        for t in (vols, out):
-            if not t[0].is_contiguous() or (N > 1 and t.stride(0) < D * H * W):
-                raise ValueError("sgm_batch: every element must be contiguous, with stride(0) >= D * H * W")
-        self._stream()
-        # (at N = 1 a tensor's stride(0) is arbitrary and is not read)
-        vs, os_ = (D * H * W, D * H * W) if N == 1 else (vols.stride(0), out.stride(0))
-        _lib.check(self.L.mvs_sgm8_batch_d(self.ctx, W, H, D, N, _ptr(vols[0]), vs, P1, P2, int(paths), _ptr(out[0]),
-                                           os_),
-                   "mvs_sgm8_batch_d")
-        return out
+        return self._sgm_batch_call("mvs_sgm8_batch_d", "sgm_batch", (torch.float32,), "float32", vols, P1, P2, paths,
+                                    out)
 
     # ---- semi-global aggregation on 16-bit integer costs (include/mvs.h at mvs_sgm8_u16_batch_d) ----
     # The tensors are torch.uint16 (this torch build allocates it and gives its data_ptr; empty() here makes
@@ -387,26 +396,10 @@ class Engine:
         of NCC cost), D <= 256; out[i] is the exact sum of the paths of the mask over vols[i].  The
         layout rules are sgm_batch's, in 2-byte elements; vols and out together are
         2 * N * 2 * D * H * W bytes."""
-        if vols.dim() != 4 or vols.dtype not in self.U16:
-            raise ValueError("sgm_u16_batch: vols must be uint16 [N, D, H, W]")
-        N, D, H, W = vols.shape
-        if N < 1:
-            raise ValueError("sgm_u16_batch: vols holds no volume")
         if int(P1) != P1 or int(P2) != P2:
             raise ValueError("sgm_u16_batch: the penalties are integers")
-        out = self.empty((N, D, H, W), torch.uint16) if out is None else out
-        if tuple(out.shape) != (N, D, H, W) or out.dtype not in self.U16:
-            raise ValueError("sgm_u16_batch: out must be uint16 [N, D, H, W]")
-        for t in (vols, out):
-            if not t[0].is_contiguous() or (N > 1 and t.stride(0) < D * H * W):
-                raise ValueError("sgm_u16_batch: every element must be contiguous, with stride(0) >= D * H * W")
-        self._stream()
-        # (at N = 1 a tensor's stride(0) is arbitrary and is not read)
-        vs, os_ = (D * H * W, D * H * W) if N == 1 else (vols.stride(0), out.stride(0))
-        _lib.check(self.L.mvs_sgm8_u16_batch_d(self.ctx, W, H, D, N, _ptr(vols[0]), vs, int(P1), int(P2), int(paths),
-                                               _ptr(out[0]), os_),
-                   "mvs_sgm8_u16_batch_d")
-        return out
+        return self._sgm_batch_call("mvs_sgm8_u16_batch_d", "sgm_u16_batch", self.U16, "uint16", vols, int(P1), int(P2),
+                                    paths, out)
 
     def wta_u16(self, agg, levels: torch.Tensor, disp=None, conf=None, want_conf: bool = True):
         """Winner (the first index of the minimum) and confidence ((c2 - best) / 2047) of a uint16
@@ -416,16 +409,10 @@ class Engine:
         D, H, W = agg.shape
         if tuple(levels.shape) != (D,) or levels.dtype != torch.float32:
             raise ValueError("wta_u16: levels must be float32 [D]")
-        disp = self.empty((H, W), torch.float32) if disp is None else disp
-        if want_conf and conf is None:
-            conf = self.empty((H, W), torch.float32)
-        for t in (disp, conf) if want_conf else (disp,):
-            if tuple(t.shape) != (H, W) or t.dtype != torch.float32:
+        for t in (disp, conf) if want_conf else (disp,):  # (one left out is made below, as asked for here)
+            if t is not None and (tuple(t.shape) != (H, W) or t.dtype != torch.float32):
                 raise ValueError("wta_u16: disp / conf must be float32 [H, W]")
-        self._stream()
-        _lib.check(self.L.mvs_wta_u16_d(self.ctx, W, H, D, _ptr(agg), _ptr(levels), _ptr(disp),
-                                        _ptr(conf) if want_conf else None), "mvs_wta_u16_d")
-        return disp, conf
+        return self._wta_call("mvs_wta_u16_d", agg, levels, disp, conf, want_conf)
 
     def _wta_sub_call(self, name, what, agg, raw, levels, disp, conf, out, want_conf):
         D, H, W = agg.shape

@@ -57,69 +57,76 @@ class PhotoConsistency:
         return spixl, rep
 
 
+def check_pixel_options(cost, subpixel, sgm, sgm_paths, sgm_batch, sgm_dtype, sgm_subpixel, arg: str = "cost"):
+    """The option rules of the per-pixel sweep, for PixelSweep and for Pipeline (which names the cost `pixel_cost`):
+    raises ValueError, and touches nothing else."""
+    ncc = f"{arg}=\"ncc\""
+    if subpixel and cost != "ncc":
+        raise ValueError(f"subpixel=True needs {ncc}: the fit is defined on the NCC cost volume")
+    if sgm and cost != "ncc":
+        raise ValueError(f"sgm=True needs {ncc}: the aggregation runs on the NCC cost volume")
+    if not 1 <= int(sgm_paths) <= 255:
+        raise ValueError("sgm_paths must be a path mask in 1..255")
+    if int(sgm_batch) < 1:
+        raise ValueError("sgm_batch must be at least 1")
+    if sgm_dtype not in ("f32", "u16"):
+        raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
+    if sgm_dtype == "u16" and not (sgm and cost == "ncc"):
+        raise ValueError(f"sgm_dtype=\"u16\" needs sgm=True and {ncc}")
+    if sgm_subpixel and not sgm:
+        raise ValueError("sgm_subpixel=True needs sgm=True: it is the sub-level disparity of the aggregate's winner")
+
+
 class PixelSweep:
-    """Per-pixel plane sweep.  cost="ncc": build-defined KxK NCC cost volume
-    [D][H][W] per reference view, then WTA + confidence (the HBM-streaming
-    pass); fused=True folds the WTA into the sweep kernel (mvs_ncc_wta_d: no
-    volume in HBM, same disp/conf bits).  cost="sad": the reference sweep at
-    S=1 grid semantics (parity).  subpixel=True (NCC only): run() also leaves
-    the sub-level disparity (the parabola fit of include/mvs.h) of the views
-    it swept in self.disp_sub; disp and conf are unchanged.  sgm=True (NCC
-    only): run() also leaves the winner and confidence of the semi-globally
-    aggregated volume (mvs_sgm_d, penalties sgm_p1 <= sgm_p2; sgm_paths is the
-    path mask, 15 = the four axis-aligned paths, 255 = with the four diagonal
-    ones, mvs_sgm8_d) in self.disp_agg and self.conf_agg [z1 - z0, H, W]:
-    per view ncc_volume ->
-    sgm -> wta, through one more [D, H, W] buffer; with fused=True the volume
-    is computed for this alone.  disp, conf and disp_sub are unchanged.
-    sgm_batch=B > 1: the views of a run are aggregated in groups of up to B,
-    one mvs_sgm8_batch_d call per group (one launch per path over the whole
-    group) through [min(B, V), D, H, W] buffers; every output keeps its bits.
-    The two buffers take 2 * B * 4 * D * H * W bytes: 10.6 GB at 1920x1080,
-    D = 128, B = 5.  With 1, the default, allocations and launches are as
-    without the option.
-    sgm_dtype="u16" (needs sgm=True and NCC cost; "f32", the default, changes
-    nothing and allocates nothing new): the aggregation runs on 16-bit integer
-    costs (include/mvs.h at mvs_sgm8_u16_batch_d).  The penalties become
-    int(round(p * 2047)) and must obey 0 <= P1 <= P2 <= 4095.  Per group of up
-    to B = sgm_batch views: ncc_volume into one reused float32 [D, H, W],
-    quant_u16 of it into q[j], one sgm_u16_batch over the group, wta_u16 of
-    agg[j] into disp_agg / conf_agg.  The buffers take
-    4 * D * H * W + 2 * B * 2 * D * H * W bytes: 6.4 GB at 1920x1080, D = 128,
-    B = 5, against 10.6 GB.  D <= 256.  disp, conf and disp_sub are as without
-    the option; disp_agg and conf_agg are those of the 16-bit definition
-    (tests/sgm16_ref.py), close to but not the float32 aggregate's.
-    sgm_subpixel=True (needs sgm=True; independent of subpixel; False, the
-    default, changes nothing): run() also leaves self.disp_agg_sub
-    [z1 - z0, H, W] beside disp_agg and conf_agg, the sub-level disparity of
-    the aggregate's winner: the parabola through the raw volume's costs at
-    that winner (include/mvs.h at mvs_wta_agg_sub_d; tests/sgm_sub_ref.py).
-    In each of the three aggregation paths the winner pass over agg becomes
-    wta_agg_sub(agg, vol) or wta_u16_sub(agg[j], q[j]): agg is still read
-    once, no buffer is added besides the output, every other output keeps
-    its bits."""
+    """Per-pixel plane sweep of the reference views [z0, z1) of a run().
+
+    cost="sad": the reference sweep at S=1 grid semantics (parity); run() gives disp alone and no option applies.
+    cost="ncc": the build-defined KxK NCC cost volume [D][H][W] of a view, then its winner and confidence (WTA).
+    run() returns (disp, conf) [z1 - z0, H, W] and leaves the options' outputs, of the same shape, in attributes.
+    No option changes the bits of another's output.
+
+    fused         the WTA is folded into the sweep kernel (mvs_ncc_wta_d): no volume in HBM, same disp / conf bits.
+                  Without it the volume is stored and read back (the HBM-streaming pass).
+    subpixel      self.disp_sub: the sub-level disparity (the parabola fit of include/mvs.h).
+    sgm           self.disp_agg, self.conf_agg: winner and confidence of the semi-globally aggregated volume
+                  (mvs_sgm_d; penalties sgm_p1 <= sgm_p2; sgm_paths is the path mask, 15 = the four axis-aligned
+                  paths, 255 = with the four diagonal ones, mvs_sgm8_d).  With fused=True the volume is computed
+                  for this alone.
+    sgm_batch=B   the views are aggregated in groups of up to min(B, V), one mvs_sgm8_batch_d call per group (one
+                  launch per path over the whole group).  With 1, the default, one mvs_sgm_d / mvs_sgm8_d call per
+                  view.
+    sgm_dtype     "u16" (needs sgm=True): the aggregation runs on 16-bit integer costs (include/mvs.h at
+                  mvs_sgm8_u16_batch_d), at every B.  The penalties become int(round(p * 2047)), self.p1_u16 and
+                  self.p2_u16, and must obey 0 <= P1 <= P2 <= 4095; D <= 256.  disp_agg and conf_agg are those of
+                  the 16-bit definition (tests/sgm16_ref.py), close to but not the float32 aggregate's.
+    sgm_subpixel  (needs sgm=True; independent of subpixel) self.disp_agg_sub: the sub-level disparity of the
+                  aggregate's winner, the parabola through the raw volume's costs at that winner (include/mvs.h at
+                  mvs_wta_agg_sub_d; tests/sgm_sub_ref.py).  The winner pass becomes one that also reads the raw
+                  volume: the aggregate is still read once and no buffer is added besides the output.
+
+    One loop serves every option set (_run_groups): per group of up to B views, for each view ncc_volume into its
+    staging volume, in the two-pass form wta (and wta_sub) of it, for "u16" quant_u16 of it into q[j]; then one
+    aggregate call over the group and the winner pass of agg[j] per view.  What the cost types differ in:
+
+                 staging of view j    raw volume   aggregate call            winner pass (with sgm_subpixel)
+    "f32", B = 1 vol                  vol          sgm(vol -> agg)           wta (wta_agg_sub)
+    "f32", B > 1 vol[j]               vol[j]       sgm_batch(vol[:g])        wta (wta_agg_sub)
+    "u16"        vol, reused          q[j]         sgm_u16_batch(q[:g])      wta_u16 (wta_u16_sub)
+
+    Buffers (self.vol, self.agg, self.q; None where not needed), with one = D * H * W:
+    * no sgm: vol float32 [D, H, W], and none with fused=True.
+    * "f32": vol and agg float32 [D, H, W] at B = 1, [B, D, H, W] above: 2 * B * 4 * one bytes, 10.6 GB at
+      1920x1080, D = 128, B = 5.
+    * "u16": vol float32 [D, H, W], q and agg uint16 [B, D, H, W]: 4 * one + 2 * B * 2 * one bytes, 6.4 GB at
+      1920x1080, D = 128, B = 5, against 10.6 GB."""
 
     def __init__(self, engine: Engine, cam: CameraArray, W: int, H: int, cost: str = "ncc", window: int = 5,
                  fused: bool = False, subpixel: bool = False, sgm: bool = False, sgm_p1: float = 0.1,
                  sgm_p2: float = 0.8, sgm_paths: int = 15, sgm_batch: int = 1, sgm_dtype: str = "f32",
                  sgm_subpixel: bool = False):
-        if subpixel and cost != "ncc":
-            raise ValueError("subpixel=True needs cost=\"ncc\": the fit is defined on the NCC cost volume")
-        if sgm and cost != "ncc":
-            raise ValueError("sgm=True needs cost=\"ncc\": the aggregation runs on the NCC cost volume")
-        if not 1 <= int(sgm_paths) <= 255:
-            raise ValueError("sgm_paths must be a path mask in 1..255")
-        if int(sgm_batch) < 1:
-            raise ValueError("sgm_batch must be at least 1")
-        if sgm_dtype not in ("f32", "u16"):
-            raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
-        if sgm_dtype == "u16" and not (sgm and cost == "ncc"):
-            raise ValueError("sgm_dtype=\"u16\" needs sgm=True and cost=\"ncc\"")
-        if sgm_subpixel and not sgm:
-            raise ValueError("sgm_subpixel=True needs sgm=True: it is the sub-level disparity of the aggregate's winner")
-        self.sgm_dtype, self.sgm_subpixel = sgm_dtype, bool(sgm_subpixel)
-        self.q = None
-        if sgm_dtype == "u16":
+        check_pixel_options(cost, subpixel, sgm, sgm_paths, sgm_batch, sgm_dtype, sgm_subpixel)
+        u16 = sgm_dtype == "u16"
+        if u16:
             self.p1_u16, self.p2_u16 = int(round(sgm_p1 * 2047)), int(round(sgm_p2 * 2047))
             if not 0 <= self.p1_u16 <= self.p2_u16 <= 4095:
                 raise ValueError("sgm_dtype=\"u16\": the penalties times 2047 must obey 0 <= P1 <= P2 <= 4095")
@@ -128,130 +135,90 @@ class PixelSweep:
         self.e, self.cam, self.W, self.H = engine, cam, W, H
         self.cost, self.K, self.fused, self.subpixel = cost, window, fused, subpixel
         self.sgm, self.sgm_p1, self.sgm_p2, self.sgm_paths = sgm, sgm_p1, sgm_p2, int(sgm_paths)
+        self.sgm_dtype, self.sgm_subpixel = sgm_dtype, bool(sgm_subpixel)
         self.disp_sub = None
         self.disp_agg = self.conf_agg = self.disp_agg_sub = None
-        self.vol = self.agg = None
-        # views per mvs_sgm8_batch_d call (1: one mvs_sgm_d / mvs_sgm8_d call per view)
-        self.sgm_batch = min(int(sgm_batch), cam.view_count) if sgm else 1
-        shape = (cam.D, H, W) if self.sgm_batch == 1 else (self.sgm_batch, cam.D, H, W)
-        if sgm_dtype == "u16":  # one float32 volume, reused; the group lives in uint16
-            self.vol = engine.empty((cam.D, H, W), torch.float32)
-            self.q = engine.empty((self.sgm_batch, cam.D, H, W), torch.uint16)
-            self.agg = engine.empty((self.sgm_batch, cam.D, H, W), torch.uint16)
-        else:
-            if cost == "ncc" and (sgm or not fused):
-                self.vol = engine.empty(shape, torch.float32)
+        self.vol = self.agg = self.q = None
+        # views per aggregate call
+        B = self.sgm_batch = min(int(sgm_batch), cam.view_count) if sgm else 1
+        one = (cam.D, H, W)
+        e = engine
+        # The cost type, stated once: _stage[j] is where ncc_volume writes view j of a group, _raw[j] the volume the
+        # aggregate call read for it (what the sub-level winner pass fits through), _aggs[j] its aggregate; _sgm is
+        # the aggregate call with the buffer it reads and its penalties; _wta / _wta_sub are the winner passes.
+        if u16:  # one float32 volume, reused; the group lives in uint16
+            self.vol = e.empty(one, torch.float32)
+            self.q = e.empty((B,) + one, torch.uint16)
+            self.agg = e.empty((B,) + one, torch.uint16)
+            self._stage, self._raw, self._aggs = [self.vol] * B, list(self.q), list(self.agg)
+            self._sgm = (e.sgm_u16_batch, self.q, self.p1_u16, self.p2_u16)
+            self._wta, self._wta_sub = e.wta_u16, e.wta_u16_sub
+        elif cost == "ncc" and (sgm or not fused):
+            self.vol = e.empty(one if B == 1 else (B,) + one, torch.float32)
+            self._stage = self._raw = [self.vol] if B == 1 else list(self.vol)
             if sgm:
-                self.agg = engine.empty(shape, torch.float32)
+                self.agg = e.empty(tuple(self.vol.shape), torch.float32)
+                self._aggs = [self.agg] if B == 1 else list(self.agg)
+                self._sgm = (e.sgm if B == 1 else e.sgm_batch, self.vol, sgm_p1, sgm_p2)
+                self._wta, self._wta_sub = e.wta, e.wta_agg_sub
         self.levels = engine.levels_dev(cam)
 
     def run(self, lab, l8, z0: int, z1: int, disp_out=None, conf_out=None, views=None):
         """Reference views [z0, z1).  views: the views whose window planes are
         built (default all; a view shard passes its block + neighbours)."""
-        n = z1 - z0
-        disp = self.e.empty((n, self.H, self.W), torch.float32) if disp_out is None else disp_out
-        conf = None
+        out = (z1 - z0, self.H, self.W)
+        disp = self.e.empty(out, torch.float32) if disp_out is None else disp_out
         if self.cost == "sad":
             self.e.sweep_pixel_sad(lab, self.cam, z0, z1, out=disp)
             return disp, None
-        conf = self.e.empty((n, self.H, self.W), torch.float32) if conf_out is None else conf_out
+        conf = self.e.empty(out, torch.float32) if conf_out is None else conf_out
         if views is None:
             box = self.e.box_stats(l8, self.K)
         else:
             V, H, W = l8.shape
             box = self.e.box_stats_views(l8, self.K, views, self.e.empty((2, V, H + (H & 1), W, 2), torch.int32))
         if self.sgm:
-            self.disp_agg = self.e.empty((n, self.H, self.W), torch.float32)
-            self.conf_agg = self.e.empty((n, self.H, self.W), torch.float32)
+            self.disp_agg = self.e.empty(out, torch.float32)
+            self.conf_agg = self.e.empty(out, torch.float32)
             if self.sgm_subpixel:
-                self.disp_agg_sub = self.e.empty((n, self.H, self.W), torch.float32)
+                self.disp_agg_sub = self.e.empty(out, torch.float32)
         if self.fused:  # every reference view of the call, runs of views per launch
             self.e.ncc_wta_range(l8, box, self.cam, z0, z1, self.K, disp=disp, conf=conf)
             if self.subpixel:  # the post-pass over the whole range, one call
                 self.disp_sub = self.e.ncc_sub_range(l8, box, self.cam, z0, z1, self.K, disp=disp)
-            if self.sgm_dtype == "u16":
-                self._run_groups_u16(l8, box, z0, z1, None, None)
-            elif self.sgm_batch > 1:
-                self._run_groups(l8, box, z0, z1, None, None)
-            elif self.sgm:  # the volume the fused sweep never stores, for the aggregation alone
-                for i, z in enumerate(range(z0, z1)):
-                    self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
-                    self._aggregate(i)
-            return disp, conf
-        if self.subpixel:
-            self.disp_sub = self.e.empty((n, self.H, self.W), torch.float32)
-        if self.sgm_dtype == "u16":
-            self._run_groups_u16(l8, box, z0, z1, disp, conf)
-            return disp, conf
-        if self.sgm_batch > 1:
+        elif self.subpixel:
+            self.disp_sub = self.e.empty(out, torch.float32)
+        if not self.fused or self.sgm:  # (fused: the volume the fused sweep never stores, for the aggregation alone)
             self._run_groups(l8, box, z0, z1, disp, conf)
-            return disp, conf
-        for i, z in enumerate(range(z0, z1)):
-            self.e.ncc_volume(l8, box, self.cam, z, self.K, out=self.vol)
-            self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
-            if self.subpixel:
-                self.e.wta_sub(self.vol, self.levels, out=self.disp_sub[i])
-            if self.sgm:
-                self._aggregate(i)
         return disp, conf
 
     def _run_groups(self, l8, box, z0: int, z1: int, disp, conf):
-        """sgm_batch > 1: the views of [z0, z1) in groups of at most sgm_batch (the last may be shorter).  Per view
-        of a group ncc_volume into vol[j] (and, in the two-pass form, where disp is given, wta / wta_sub of it), one
-        sgm_batch over the group, then the winner pass (_winner) of agg[j] into view i of disp_agg / conf_agg."""
+        """The views of [z0, z1) in groups of at most sgm_batch (the last may be shorter): the class docstring's
+        loop.  View j of a group is view i of the outputs."""
         B = self.sgm_batch
         for g0 in range(z0, z1, B):
             g = min(B, z1 - g0)
             for j in range(g):
-                i = g0 - z0 + j
-                self.e.ncc_volume(l8, box, self.cam, g0 + j, self.K, out=self.vol[j])
-                if disp is not None:
-                    self.e.wta(self.vol[j], self.levels, disp=disp[i], conf=conf[i])
+                i, vol = g0 - z0 + j, self._stage[j]
+                self.e.ncc_volume(l8, box, self.cam, g0 + j, self.K, out=vol)
+                if not self.fused:
+                    self.e.wta(vol, self.levels, disp=disp[i], conf=conf[i])
                     if self.subpixel:
-                        self.e.wta_sub(self.vol[j], self.levels, out=self.disp_sub[i])
-            self.e.sgm_batch(self.vol[:g], self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg[:g])
-            for j in range(g):
-                i = g0 - z0 + j
-                self._winner(self.agg[j], self.vol[j], i)
-
-    def _run_groups_u16(self, l8, box, z0: int, z1: int, disp, conf):
-        """sgm_dtype="u16": _run_groups with the group in uint16.  Per view of a group ncc_volume into the one
-        float32 volume (and, in the two-pass form, wta / wta_sub of it), quant_u16 of it into q[j]; one sgm_u16_batch
-        over the group; wta_u16 of agg[j] (with sgm_subpixel wta_u16_sub of agg[j] and q[j]) into view i of disp_agg /
-        conf_agg."""
-        B = self.sgm_batch
-        for g0 in range(z0, z1, B):
-            g = min(B, z1 - g0)
-            for j in range(g):
-                i = g0 - z0 + j
-                self.e.ncc_volume(l8, box, self.cam, g0 + j, self.K, out=self.vol)
-                if disp is not None:
-                    self.e.wta(self.vol, self.levels, disp=disp[i], conf=conf[i])
-                    if self.subpixel:
-                        self.e.wta_sub(self.vol, self.levels, out=self.disp_sub[i])
-                self.e.quant_u16(self.vol, out=self.q[j])
-            self.e.sgm_u16_batch(self.q[:g], self.p1_u16, self.p2_u16, self.sgm_paths, out=self.agg[:g])
+                        self.e.wta_sub(vol, self.levels, out=self.disp_sub[i])
+                if self.q is not None:
+                    self.e.quant_u16(vol, out=self.q[j])
+            if not self.sgm:
+                continue
+            call, src, p1, p2 = self._sgm
+            s = slice(None) if self.agg.dim() == 3 else slice(g)  # sgm takes the one volume, a batch call the group's
+            call(src[s], p1, p2, self.sgm_paths, out=self.agg[s])
             for j in range(g):
                 i = g0 - z0 + j
                 if self.sgm_subpixel:
-                    self.e.wta_u16_sub(self.agg[j], self.q[j], self.levels, disp=self.disp_agg[i],
-                                       conf=self.conf_agg[i], out=self.disp_agg_sub[i])
+                    self._wta_sub(self._aggs[j], self._raw[j], self.levels, disp=self.disp_agg[i],
+                                  conf=self.conf_agg[i], out=self.disp_agg_sub[i])
                 else:
-                    self.e.wta_u16(self.agg[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
-
-    def _aggregate(self, i: int):
-        """self.vol -> sgm -> the winner pass into view i of disp_agg / conf_agg."""
-        self.e.sgm(self.vol, self.sgm_p1, self.sgm_p2, self.sgm_paths, out=self.agg)
-        self._winner(self.agg, self.vol, i)
-
-    def _winner(self, agg, vol, i: int):
-        """The float32 aggregate's winner pass into view i: wta, or with sgm_subpixel wta_agg_sub, which also fits
-        through vol at that winner."""
-        if self.sgm_subpixel:
-            self.e.wta_agg_sub(agg, vol, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i],
-                               out=self.disp_agg_sub[i])
-        else:
-            self.e.wta(agg, self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
+                    self._wta(self._aggs[j], self.levels, disp=self.disp_agg[i], conf=self.conf_agg[i])
 
 
 class DepthRefinement:
@@ -316,8 +283,7 @@ class Pipeline:
         PixelSweep; its buffers are 4 * D * H * W + 2 * B * 2 * D * H * W bytes.
         sgm_subpixel: with sgm=True, the result also carries disp_agg_sub, the sub-level disparity of the aggregate's
         winner (see PixelSweep)."""
-        if int(sgm_batch) < 1:
-            raise ValueError("sgm_batch must be at least 1")
+        check_pixel_options(pixel_cost, subpixel, sgm, sgm_paths, sgm_batch, sgm_dtype, sgm_subpixel, arg="pixel_cost")
         self.e, self.st, self.W, self.H = engine, settings, W, H
         vs = view_subset if view_subset is not None else params.neighbour_lists(
             settings.array_width, settings.array_height, settings.neib_hor, settings.neib_ver)
@@ -326,16 +292,6 @@ class Pipeline:
         self.cam = CameraArray(settings.array_width, settings.bl_ratio, levels, mat, num)
         self.slic = SLIC(engine, settings)
         self.photo = PhotoConsistency(engine, self.cam, settings.spixl_size)
-        if subpixel and pixel_cost != "ncc":
-            raise ValueError("subpixel=True needs pixel_cost=\"ncc\"")
-        if sgm and pixel_cost != "ncc":
-            raise ValueError("sgm=True needs pixel_cost=\"ncc\"")
-        if sgm_dtype not in ("f32", "u16"):
-            raise ValueError("sgm_dtype must be \"f32\" or \"u16\"")
-        if sgm_dtype == "u16" and not (sgm and pixel_cost == "ncc"):
-            raise ValueError("sgm_dtype=\"u16\" needs sgm=True and pixel_cost=\"ncc\"")
-        if sgm_subpixel and not sgm:
-            raise ValueError("sgm_subpixel=True needs sgm=True")
         self.pixel = (PixelSweep(engine, self.cam, W, H, pixel_cost, settings.window, fused, subpixel, sgm, sgm_p1,
                                  sgm_p2, sgm_paths, sgm_batch, sgm_dtype, sgm_subpixel)
                       if pixel_cost else None)

@@ -1,4 +1,4 @@
-// plan_sgm16_batch, sgm16_batch_vec_ok and the piece phase (csrc/launch_plan.{h,cpp}) on the CPU: the argument
+// plan_sgm_batch at kSgmU16, sgm_piece_vec_ok and the piece phase (csrc/launch_plan.{h,cpp}) on the CPU: the argument
 // rules of mvs_sgm8_u16_batch_d in 2-byte elements, against brute force.
 //  1. N in {1, 2, 3, 5, 65535, 65536, 0, -1}, strides D H W + {-1, 0, 1, 7, 8, 9} for each buffer and base offsets
 //     of {0, 1, 3, 7} elements for each buffer: the planner's error equals the rules of include/mvs.h, vec_ok equals
@@ -7,12 +7,12 @@
 //  2. Odd addresses, the level limit (256 accepted, 257 unsupported), span pairs (nested, interleaved, abutting).
 //  3. Element strides near 2^41 with N = 65535: the spans must be formed without overflow.
 //  4. The phase: for every line address mod 16 bytes (even addresses), every line length n in 1..40 and every
-//     pixel x, the piece of pixel x starts at a multiple of 16 bytes, holds x at element sgm16_piece_elem, and
-//     sgm16_piece_inside equals "all eight pixels of that piece lie in [0, n)"; the pieces inside a line are
+//     pixel x, the piece of pixel x starts at a multiple of 16 bytes, holds x at element sgm_piece_elem, and
+//     sgm_piece_inside equals "all eight pixels of that piece lie in [0, n)"; the pieces inside a line are
 //     disjoint and every pixel is either in exactly one of them or handled singly.
 //  5. The same for the general piece arithmetic (sgm_piece_phase, sgm_piece_elem, sgm_piece_inside) at both piece
-//     sizes, 4 float32 and 8 uint16 pixels, and sgm_piece_vec_ok against its two instances.
-// Links only the planner; built with the address and undefined-behaviour sanitizers (Makefile: plancheck).
+//     sizes, 4 float32 and 8 uint16 pixels, and sgm_piece_vec_ok against its rule.
+// Links only the planner; built with the address and undefined-behaviour sanitizers (Makefile: sgmplancheck).
 // Prints one line per case of 1 to 4.  Exit status 0: every check held.
 #include <cstdint>
 #include <cstdio>
@@ -42,8 +42,8 @@ static bool spans_overlap(int D, int H, int W, int N, uint64_t va, uint64_t vs, 
   return !(v1 <= a0 || a1 <= v0);
 }
 
-static Sgm16BatchPlan check(int W, int H, int D, int N, uint64_t va, uint64_t vs, uint64_t aa, uint64_t as) {
-  const Sgm16BatchPlan p = plan_sgm16_batch(W, H, D, N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as);
+static SgmBatchPlan check(int W, int H, int D, int N, uint64_t va, uint64_t vs, uint64_t aa, uint64_t as) {
+  const SgmBatchPlan p = plan_sgm_batch(kSgmU16, W, H, D, N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as);
   std::printf("W=%d H=%d D=%d N=%d vol=%llu+%llu agg=%llu+%llu -> %s grid_y=%u vec_ok=%d\n", W, H, D, N,
               (unsigned long long)va, (unsigned long long)vs, (unsigned long long)aa, (unsigned long long)as,
               p.err ? p.err : "ok", p.grid_y, (int)p.vec_ok);
@@ -67,7 +67,7 @@ static Sgm16BatchPlan check(int W, int H, int D, int N, uint64_t va, uint64_t vs
   for (int i = 0; i < (N < 16 ? N : 16); i++)
     congruent = congruent && ((va + 2 * (uint64_t)i * vs) & 15) == ((aa + 2 * (uint64_t)i * as) & 15);
   CHECK(p.vec_ok == congruent);
-  CHECK(p.vec_ok == sgm16_batch_vec_ok(N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as));
+  CHECK(p.vec_ok == sgm_piece_vec_ok(kSgm16Piece, N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as));
   return p;
 }
 
@@ -86,7 +86,7 @@ int main() {
         for (int da : ds)
           for (int ov : os)
             for (int oa : os) {
-              const Sgm16BatchPlan p = check(W, H, D, N, vbase + 2 * ov, dhw + dv, abase + 2 * oa, dhw + da);
+              const SgmBatchPlan p = check(W, H, D, N, vbase + 2 * ov, dhw + dv, abase + 2 * oa, dhw + da);
               if (!p.err) (p.vec_ok ? vec : scalar)++;
             }
     CHECK(vec > 0 && scalar > 0);
@@ -109,8 +109,8 @@ int main() {
     CHECK(check(W, H, D, 1, v, 3 * dhw, v + e * dhw, dhw).err == nullptr);  // (N = 1: no gap, the stride is not used)
     CHECK(check(W, H, D, N, v, 3 * dhw, v + e * dhw, dhw).err != nullptr);  // agg inside vol's gap
     CHECK(check(W, H, D, 1, v, dhw, v + e * (dhw - 1), dhw).err != nullptr);
-    CHECK(plan_sgm16_batch(0, H, D, N, v, dhw, 1ull << 30, dhw).err != nullptr);
-    CHECK(plan_sgm16_batch((1 << 14) + 1, 1 << 13, D, N, v, 1ull << 50, 1ull << 62, 1ull << 50).err != nullptr);
+    CHECK(plan_sgm_batch(kSgmU16, 0, H, D, N, v, dhw, 1ull << 30, dhw).err != nullptr);
+    CHECK(plan_sgm_batch(kSgmU16, (1 << 14) + 1, 1 << 13, D, N, v, 1ull << 50, 1ull << 62, 1ull << 50).err != nullptr);
   }
   // 3. the largest planes (W H = 2^27) at 256 levels are 2^35 elements; strides near 2^41 with N = 65535
   {
@@ -135,17 +135,17 @@ int main() {
   {
     int whole = 0, single = 0;
     for (uint64_t a = 4096; a < 4096 + 16; a += 2) {
-      const int ph = sgm16_phase((uintptr_t)a);
+      const int ph = sgm_piece_phase(kSgm16Piece, (uintptr_t)a);
       CHECK(ph == (int)((a / 2) % 8));
       for (int n = 1; n <= 40; n++) {
         int owner[40];
         for (int x = 0; x < n; x++) owner[x] = -2;  // -2: unseen, -1: single, else the piece's first pixel
         for (int x = 0; x < n; x++) {
-          const int j = sgm16_piece_elem(ph, x), xs = x - j;
+          const int j = sgm_piece_elem(kSgm16Piece, ph, x), xs = x - j;
           CHECK(j >= 0 && j < kSgm16Piece);
           CHECK(((int64_t)a + 2 * (int64_t)xs) % 16 == 0);  // the piece's own address, xs may be negative
           const bool inside = xs >= 0 && xs + kSgm16Piece - 1 < n;
-          CHECK(sgm16_piece_inside(ph, x, n) == inside);
+          CHECK(sgm_piece_inside(kSgm16Piece, ph, x, n) == inside);
           owner[x] = inside ? xs : -1;
           (inside ? whole : single)++;
         }
@@ -169,7 +169,6 @@ int main() {
     for (uint64_t a = 4096; a < 4096 + 16; a += elem) {
       const int ph = sgm_piece_phase(piece, (uintptr_t)a);
       CHECK(ph == (int)((a / elem) % piece));
-      if (piece == kSgm16Piece) CHECK(ph == sgm16_phase((uintptr_t)a));
       for (int n = 1; n <= 40; n++) {
         int owner[40];
         for (int x = 0; x < n; x++) {
@@ -178,7 +177,6 @@ int main() {
           CHECK(((int64_t)a + elem * (int64_t)xs) % 16 == 0);
           const bool inside = xs >= 0 && xs + piece - 1 < n;
           CHECK(sgm_piece_inside(piece, ph, x, n) == inside);
-          if (piece == kSgm16Piece) CHECK(j == sgm16_piece_elem(ph, x) && inside == sgm16_piece_inside(ph, x, n));
           owner[x] = inside ? xs : -1;
           (inside ? whole : single)++;
         }
@@ -197,8 +195,6 @@ int main() {
         for (uint64_t ds = 0; ds < 9; ds++) {
           const bool ok = sgm_piece_vec_ok(piece, N, 4096, 1000 + ds, 8192 + da, 1000);
           CHECK(ok == (da == 0 && (N == 1 || ds % piece == 0)));
-          CHECK(ok == (piece == kSgmPiece ? sgm_batch_vec_ok(N, 4096, 1000 + ds, 8192 + da, 1000)
-                                          : sgm16_batch_vec_ok(N, 4096, 1000 + ds, 8192 + da, 1000)));
         }
   }
   if (g_bad) std::printf("%d checks failed\n", g_bad);

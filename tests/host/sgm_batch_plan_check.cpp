@@ -8,7 +8,7 @@
 // rule equals an interval test on the spans.  Overlapping, nested and abutting
 // span pairs follow, then the largest shape (W H = 2^27, D = 16384, N = 65535),
 // whose spans must be formed without overflow.  Links only the planner; built
-// with the address and undefined-behaviour sanitizers (Makefile: plancheck).
+// with the address and undefined-behaviour sanitizers (Makefile: sgmplancheck).
 // Prints one line per case.  Exit status 0: every check held.
 #include <cstdint>
 #include <cstdio>
@@ -41,7 +41,7 @@ static bool spans_overlap(int D, int H, int W, int N, uint64_t va, uint64_t vs, 
 
 // one case against the rules; returns the plan
 static SgmBatchPlan check(int W, int H, int D, int N, uint64_t va, uint64_t vs, uint64_t aa, uint64_t as) {
-  const SgmBatchPlan p = plan_sgm_batch(W, H, D, N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as);
+  const SgmBatchPlan p = plan_sgm_batch(kSgmF32, W, H, D, N, (uintptr_t)va, (size_t)vs, (uintptr_t)aa, (size_t)as);
   std::printf("W=%d H=%d D=%d N=%d vol=%llu+%llu agg=%llu+%llu -> %s grid_y=%u vec_ok=%d\n", W, H, D, N,
               (unsigned long long)va, (unsigned long long)vs, (unsigned long long)aa, (unsigned long long)as,
               p.err ? p.err : "ok", p.grid_y, (int)p.vec_ok);
@@ -116,9 +116,9 @@ int main() {
     CHECK(check(W2, H2, D2, N, 1ull << 62, huge, 4096, big).err == nullptr);
     CHECK(check(W2, H2, D2, N, 4096, huge, 1ull << 62, big).err != nullptr);
     // one more pixel, one more level
-    CHECK(plan_sgm_batch(W2 + 1, H2, D2, N, 4096, 2 * big, 4096 + 16 * span, 2 * big).err != nullptr);
-    CHECK(plan_sgm_batch(W2, H2, D2 + 1, N, 4096, 2 * big, 4096 + 16 * span, 2 * big).err != nullptr);
-    CHECK(plan_sgm_batch(0, H2, D2, N, 4096, big, 4096 + span, big).err != nullptr);
+    CHECK(plan_sgm_batch(kSgmF32, W2 + 1, H2, D2, N, 4096, 2 * big, 4096 + 16 * span, 2 * big).err != nullptr);
+    CHECK(plan_sgm_batch(kSgmF32, W2, H2, D2 + 1, N, 4096, 2 * big, 4096 + 16 * span, 2 * big).err != nullptr);
+    CHECK(plan_sgm_batch(kSgmF32, 0, H2, D2, N, 4096, big, 4096 + span, big).err != nullptr);
   }
   if (g_bad) std::printf("%d checks failed\n", g_bad);
   return g_bad ? 1 : 0;

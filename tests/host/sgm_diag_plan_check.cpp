@@ -7,7 +7,7 @@
 // is visited exactly once, and each visit's predecessor (x - dx, y - dy) is the
 // pixel the same lane or line visited one step earlier, or lies outside the
 // image on the lane's or line's first visit.  Links only the planner; built
-// with the address and undefined-behaviour sanitizers (Makefile: plancheck).
+// with the address and undefined-behaviour sanitizers (Makefile: sgmplancheck).
 // Exit status 0: every invariant held.
 #include <climits>
 #include <cstdio>
@@ -43,7 +43,7 @@ static bool visit(int W, int H, int dx, int dy, int x, int y, int& px, int& py, 
 }
 
 static void check(int W, int H, int D, int path) {
-  const SgmDiagPlan p = plan_sgm_diag(W, H, D, path);
+  const SgmPlan p = plan_sgm_diag(W, H, D, path);
   if (p.err) {
     std::printf("W=%d H=%d D=%d path=%d error: %s\n", W, H, D, path, p.err);
     g_bad++;

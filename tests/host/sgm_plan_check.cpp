@@ -1,7 +1,7 @@
 // plan_sgm (csrc/launch_plan.cpp) on the CPU: walks image sizes and level
 // counts on and around every threshold of the planner, checks each plan's
 // invariants and prints one line per case.  Links only the planner; built
-// with the address and undefined-behaviour sanitizers (Makefile: plancheck).
+// with the address and undefined-behaviour sanitizers (Makefile: sgmplancheck).
 // Exit status 0: every invariant held.
 #include <climits>
 #include <cstdio>

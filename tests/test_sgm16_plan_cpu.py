@@ -1,4 +1,4 @@
-"""plan_sgm16_batch, sgm16_batch_vec_ok and the piece phase (csrc/launch_plan.cpp,
+"""plan_sgm_batch at kSgmU16, sgm_piece_vec_ok and the piece phase (csrc/launch_plan.cpp,
 launch_plan.h), the argument rules and the kernel-form choice of
 mvs_sgm8_u16_batch_d, on the CPU: tests/host/sgm16_plan_check.cpp links only
 the planner (plain C++, g++, address and undefined-behaviour sanitizers) and
