@@ -1,20 +1,16 @@
-// Matrix-core form of the fused NCC sweep + WTA (K = 5): the definition and
-// the outputs are ncc.hip's (k_ncc_volume with FUSE), bit for bit;
+// Matrix-core form of the fused NCC sweep + WTA (K = 5 and K = 7): the
+// definition and the outputs are ncc.hip's (k_ncc_volume with FUSE), bit for bit;
 // plan_ncc_launches (ncc_plan.cpp) picks it per reference view.  See the comment at
 // NccMRec for the formulation.
 #include <type_traits>
 
 #include "ncc_common.h"
 
-#ifndef MVS_MFMA_SPLIT
-#define MVS_MFMA_SPLIT 1
-#endif
-
 namespace mvs {
 namespace ncc {
 namespace {
 
-// ---- matrix-core form of the fused sweep (K = 5) ----
+// ---- matrix-core form of the fused sweep (written out for K = 5; K = 7: at k_ncc_mfma) ----
 //
 // The correlation Srp'(x, y, d) = sum_{j, i} r'(x+i, y+j) p'(x+i-tx(d), y+j)
 // as a GEMM whose output lands in the SAME (pixel, level) layout for every
@@ -72,7 +68,8 @@ static_assert(sizeof(NccMRec) == 4 * kRecWords, "one 128-B record per (chunk, ne
 // second accumulating onto the first).  TAIL: D % DC != 0, the last chunk carries dummy levels past the
 // end.  NDB: 16-level blocks per chunk (DC = 16 NDB levels per step).  NB:
 // band buffers (2: step t+1's bands land while step t computes; 1: staged at
-// the start of each step, the other resident workgroup computing meanwhile).
+// the start of each step, the other resident workgroup computing meanwhile;
+// VERT only -- horizontal lists are always double-buffered).
 // DBG (timing probe only, MVS_NCC_MFMA_DBG): 1 skips the MFMAs and the
 // finish (band DMA, barriers, fold and merge stay), 2 skips the band DMA
 template <int K, int BW, bool TAIL, bool VERT, int NDB, int NB, int DBG = 0>
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
   static_assert(NDB == 1 || NDB == 2, "one or two 16-level blocks per chunk");
   static_assert(K == 5 || K == 7, "5 x 5 or 7 x 7 windows");
   static_assert(K == 5 || !VERT, "K = 7: horizontal lists only");
-  static_assert(VERT || NB == 2 || NB == 3, "the horizontal form is double- or triple-buffered");
+  static_assert(VERT || NB == 2, "the horizontal form is double-buffered");
   static_assert(VERT || NDB == (K == 5 ? 2 : 1), "horizontal chunks: 32 levels (K = 5), 16 (K = 7: A takes 32 VGPRs)");
   constexpr int R = K / 2, NW = 8, TH = 8, DC = 16 * NDB, NK = K * K;
   // pixel blocks per wave: XB across (BXW columns each) x NYB down; MF MFMAs per block and level block
@@ -92,7 +89,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
   // rows (row pairs g, g + 1) fall on different banks when the shift per level
   // is even (|dx| = 2: conflict-free instead of 2-way)
   constexpr int BWP = BW + 1;
-  constexpr bool SPLIT = MVS_MFMA_SPLIT;
   extern __shared__ __align__(16) uint8_t smem[];
   const int nbuf = (a.pk_pairs + a.st_pairs) * BWP;  // uint4 per neighbour buffer
   u32x4* nbase = (u32x4*)smem;                      // 2 x {npk[pk_pairs][BW], nst[st_pairs][BW]}
@@ -135,6 +131,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     int tx, shp;      // raw record words: nothing computed on them until they are used
     unsigned lo, hi;  // the neighbour plane's byte offset
   };
+  // (n, the step's neighbour, is not used: the record holds the plane's offset.  It, nmod below
+  // and the !VERT branch of stage, which horizontal lists never call, are dead source that
+  // the horizontal kernels' register allocation depends on all the same: without any one of
+  // them the K = 5 kernels, at the 128-VGPR cap, spill 12 to 20 B.  DESIGN.md §4i)
   auto load_info = [&](int t, int n) -> StepInfo {
     const NccMRec& e = rec[t];
     return StepInfo{e.txmax, e.shp, e.off_lo, e.off_hi};
@@ -167,6 +167,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
       }
     }
   };
+  // VERT's staging (the prologue, the NB = 1 restage, the look-ahead); horizontal lists go through stage_h
   auto stage = [&](int t, int n, int b) {
     if (DBG == 2) return;
     const NccMRec& e = rec[t];
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     u32x4* npk = nbase + b * nbuf;
     u32x4* nst = npk + a.pk_pairs * BWP;
     const int xb0 = x0 - e.txmax + lane;
-    if constexpr (!VERT) {
+    if constexpr (!VERT) {  // never called (see load_info)
       for (int cb = 0; cb < nblk; cb++) {
         const int c0 = min(cb * 64, span);
         const int xx = min(max(xb0 + c0, 0), W - 1);
@@ -198,16 +199,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
 
   // the steps' level -> band column offsets, into LDS (before the pipeline)
   for (int i = tid; i < T * DC / 2; i += NW * 64) ((int*)colo_l)[i] = rec[i / (DC / 2)].colo[i % (DC / 2)];
-  // step t's scalars (cur) and step t+1's (nxt); horizontal lists only
-  // NB = 3 (horizontal): nx2 = step t+2's, staged at step t, two steps ahead
-  auto nmod = [&](int v) { return v >= nn ? v - nn : v; };  // (v < 2 nn)
-  StepInfo cur{}, nxt{}, nx2{};
+  auto nmod = [&](int v) { return v >= nn ? v - nn : v; };  // (v < 2 nn) a step's neighbour: for load_info's n only
+  // step t's scalars (cur) and step t+1's (nxt): horizontal lists only (VERT
+  // reads rec[t] where it needs it; step() names cur in both, so they are
+  // declared for both and stay empty under VERT)
+  StepInfo cur{}, nxt{};
   if constexpr (!VERT) {
     cur = load_info(0, 0);
-    if (T > 1) nxt = load_info(1, nmod(1 % nn));
-    if (NB == 3 && T > 2) nx2 = load_info(2, nmod(2 % nn));
+    if (T > 1) nxt = load_info(1, nmod(1));
     stage_h(cur, 0);
-    if (NB == 3 && T > 1) stage_h(nxt, 1);
   } else {
     stage(0, 0, 0);
   }
@@ -381,22 +381,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
       }
   };
 
-  int bt = 0;  // NB = 3: the buffer of step t (t % 3)
   // one pipeline step t = c * nn + n (chunks outer, neighbours inner; the
   // chunk's first neighbour assigns E, as k_ncc_volume's PEEL)
   auto step = [&](int t, int n, int cprev, auto first) {
     constexpr bool FIRST = decltype(first)::value;
     const int n1 = n + 1 == nn ? 0 : n + 1;
-    StepInfo pf{};  // step t+NB's scalars, issued now, used NB - 1 steps on
+    StepInfo pf{};  // horizontal: step t+2's scalars, issued now, step t+1's nxt at the end of this step
     if constexpr (!VERT) {
-      const int n2 = n1 + 1 == nn ? 0 : n1 + 1;
-      if (t + NB < T) pf = load_info(t + NB, NB == 2 ? n2 : nmod(n2 + 1));
+      if (t + 2 < T) pf = load_info(t + 2, nmod(n1 + 1));
     }
     if (NB == 1 && t > 0) {  // this step's bands into the one buffer (step 0's: before the loop)
       stage(t, n, 0);
       __syncthreads();  // vmcnt(0): landed, for every wave
     }
-    u32x4* const nbuf_t = nbase + (NB == 2 ? (t & 1) : NB == 3 ? bt : 0) * nbuf;
+    u32x4* const nbuf_t = nbase + (NB == 2 ? t & 1 : 0) * nbuf;
     // A block's B entry sits at column x0b - tx, up to 3 columns left of its
     // cells' neighbour pixels: a valid cell (neighbour column 2, xx = 3) reads
     // the entry of image column -1, which the clamped DMA filled with column
@@ -417,15 +415,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         __syncthreads();
       }
     }
-    int pieces = 0;  // NB = 3: this wave's LDS-DMA pieces of step t+2 (the barrier's count)
-    if constexpr (!VERT && NB == 2) {
+    // the look-ahead: step t+1's bands into the other buffer, landing while this step computes
+    if constexpr (!VERT) {
       if (t + 1 < T) stage_h(nxt, (t + 1) & 1);
-    } else if constexpr (!VERT) {
-      if (t + 2 < T) {
-        stage_h(nx2, bt == 0 ? 2 : bt - 1);  // (t + 2) % 3
-        const int nb2 = (((nx2.shp >> 16) & 0xff) + 127) >> 6;
-        pieces = (wave < bhp ? nb2 : 0) + (wave < shp ? nb2 : 0);
-      }
     } else {
       if (NB == 2 && t + 1 < T) stage(t + 1, n1, (t + 1) & 1);
     }
@@ -519,29 +511,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
         for (int mf = 0; mf < MF; mf++) bv[mf] = bread(xb, yb, db, mf);
         f32x4 s0, s1;
         sread(xb, yb, db, s0, s1);
-        if (SPLIT) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
         i32x4 acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][0], bv[0], bias, 0, 0, 0);
         if constexpr (MF == 2) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[k][1], bv[1], acc, 0, 0, 0);
         finish(xb, yb, db, acc, nsr, s0, s1);
       }
     }
-    if constexpr (!VERT && NB == 3) {
-      // step t+1's bands landed (this wave's pieces of it are older than its
-      // `pieces` of step t+2: loads retire in order), then the barrier: every
-      // wave's; buffer t % 3 is free for step t+3 (staged at step t+1)
-      wait_vm_barrier(pieces);  // (a memory clobber: no LDS access moves across it; no vmcnt(0) added)
-    } else {
-      __syncthreads();  // NB = 2: step t+1's bands landed, this buffer free for t+2; NB = 1: free for t+1
-    }
+    __syncthreads();  // NB = 2: step t+1's bands landed, this buffer free for t+2; NB = 1: free for t+1
     if constexpr (!VERT) {
       cur = nxt;
-      if constexpr (NB == 3) {
-        nxt = nx2;
-        nx2 = pf;
-        bt = bt == 2 ? 0 : bt + 1;
-      } else {
-        nxt = pf;
-      }
+      nxt = pf;
     }
   };
   {
@@ -684,9 +663,8 @@ int launch_ncc_mfma(const NccCall& c) {
     return no_kernel();
   }
   // horizontal lists: pitch 128 | 192, the tail kernels 192
-  if (L.K == 7 && L.NDB == 1) {  // 16-level chunks; the 128-column pitch double- or triple-buffered
+  if (L.K == 7 && L.NDB == 1) {  // 16-level chunks
     if (L.TAIL) return L.BW == 192 && L.NB == 2 ? launch_mfma_bw<7, 192, true, false, 1, 2>(c) : no_kernel();
-    if (L.BW == 128 && L.NB == 3) return launch_mfma_bw<7, 128, false, false, 1, 3>(c);
     if (L.BW == 128 && L.NB == 2) return launch_mfma_bw<7, 128, false, false, 1, 2>(c);
     return L.BW == 192 && L.NB == 2 ? launch_mfma_bw<7, 192, false, false, 1, 2>(c) : no_kernel();
   }

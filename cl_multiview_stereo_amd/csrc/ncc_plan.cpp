@@ -34,7 +34,6 @@ NccTuning ncc_tuning(int force_nw, int force_dpw, int force_bw, int force_genera
   t.mfma = env_int("MVS_NCC_MFMA", 1);
   t.mfma_v = env_int("MVS_NCC_MFMA_V", 1);
   t.mfma7 = env_int("MVS_NCC_MFMA7", 1);
-  t.mfma7_nb = env_int("MVS_NCC_MFMA7_NB", 0);
   t.mfma_dbg = env_int("MVS_NCC_MFMA_DBG", 0);
   t.run = std::max(1, std::min(kMaxRef, env_int("MVS_NCC_RUN", kMaxRef)));
   t.plane32 = env_int("MVS_NCC_PLANE32", 1);
@@ -521,19 +520,12 @@ bool plan_ncc_launches(const NccTuning& t, int V, int W, int H, int K, int D, co
       L.NB = f.nb;
       L.BW = mfma_pitch(f.vert, L.TAIL, K, run.width);
       L.tmax = run.steps;
-      // K = 7 at the 128-column pitch: MVS_NCC_MFMA7_NB=3 takes the triple-
-      // buffered form (bands two steps ahead; measured slower, opt-in) where
-      // it keeps two workgroups per CU
-      if (K == 7 && !L.TAIL && L.BW == 128 && t.mfma7_nb == 3 &&
-          mfma_lds_bytes(128, 3, run.pk_pairs + run.st_pairs, L.tmax, dc) <= kLdsTwo)
-        L.NB = 3;
       // timing probes, on the three shapes that have one (C5's, C2's, C4's interior lists)
       if (t.mfma_dbg && !L.TAIL) {
         if (f.vert) {
           if (L.NDB == 1 && L.NB == 2 && L.BW == 80 && (t.mfma_dbg == 1 || t.mfma_dbg == 2)) L.DBG = t.mfma_dbg;
         } else if ((K == 7 && L.BW == 128) || (K == 5 && L.BW == 192)) {
           L.DBG = t.mfma_dbg == 1 ? 1 : 2;
-          L.NB = 2;
         }
       }
       L.lds = mfma_lds_bytes(L.BW, L.NB, run.pk_pairs + run.st_pairs, L.tmax, dc);

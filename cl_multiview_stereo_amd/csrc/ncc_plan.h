@@ -48,7 +48,6 @@ struct NccTuning {
   int mfma = 1;         // MVS_NCC_MFMA: 0 keeps the scalar kernels
   int mfma_v = 1;       // MVS_NCC_MFMA_V: vertical / diagonal lists: 0 scalar, 1 automatic, 22|21|12|11 that form
   int mfma7 = 1;        // MVS_NCC_MFMA7: 0 keeps the scalar kernels at K = 7
-  int mfma7_nb = 0;     // MVS_NCC_MFMA7_NB: 3 takes K = 7's triple-buffered form where it fits
   int mfma_dbg = 0;     // MVS_NCC_MFMA_DBG: timing probes (1 no MFMA / finish, 2 no band DMA)
   int run = kMaxRef;    // MVS_NCC_RUN: reference views per launch at most
   int plane32 = 1;      // MVS_NCC_PLANE32: 0 stages the scalar kernels' bands by 64-bit addresses

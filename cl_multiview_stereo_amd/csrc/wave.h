@@ -1,5 +1,5 @@
 // Wave-level device helpers shared by the HIP units (no stage knowledge): short vector types, LDS-DMA
-// pointer types, buffer descriptors, vector-memory waits, the lane id and the exact round-half-away.
+// pointer types, buffer descriptors, the vector-memory wait, the lane id and the exact round-half-away.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,30 +42,6 @@ __device__ __forceinline__ void wait_vm(int n) {
     case 5: __builtin_amdgcn_s_waitcnt(0x0f75); break;
     default: __builtin_amdgcn_s_waitcnt(0x0f76); break;
   }
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform n in [0, 6] (n > 6: vmcnt(6)), then
-// s_barrier -- the selection inside one asm block, so the compiler sees no
-// branch (a C-level switch split the step and spilled the fold's registers)
-__device__ __forceinline__ void wait_vm_barrier(int n) {
-  asm volatile(
-      "s_cmp_eq_u32 %0, 0\n\ts_cbranch_scc1 10f\n\t"
-      "s_cmp_eq_u32 %0, 1\n\ts_cbranch_scc1 11f\n\t"
-      "s_cmp_eq_u32 %0, 2\n\ts_cbranch_scc1 12f\n\t"
-      "s_cmp_eq_u32 %0, 3\n\ts_cbranch_scc1 13f\n\t"
-      "s_cmp_eq_u32 %0, 4\n\ts_cbranch_scc1 14f\n\t"
-      "s_cmp_eq_u32 %0, 5\n\ts_cbranch_scc1 15f\n\t"
-      "s_waitcnt vmcnt(6)\n\ts_branch 19f\n"
-      "10:\n\ts_waitcnt vmcnt(0)\n\ts_branch 19f\n"
-      "11:\n\ts_waitcnt vmcnt(1)\n\ts_branch 19f\n"
-      "12:\n\ts_waitcnt vmcnt(2)\n\ts_branch 19f\n"
-      "13:\n\ts_waitcnt vmcnt(3)\n\ts_branch 19f\n"
-      "14:\n\ts_waitcnt vmcnt(4)\n\ts_branch 19f\n"
-      "15:\n\ts_waitcnt vmcnt(5)\n"
-      "19:\n\ts_barrier"
-      :
-      : "s"(n)
-      : "memory", "scc");
 }
 
 // the lane id, recomputed where it is used (volatile: never hoisted, so it is

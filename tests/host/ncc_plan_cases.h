@@ -125,7 +125,6 @@ inline std::vector<Case> cases() {
   add("horizontal_k5", {}, {c2, h5n, h5t, h5tn});
   add("horizontal_k7", {}, {c5, h7w, h7t});
   add("horizontal_k7_mfma7_off", {{"MVS_NCC_MFMA7", "0"}}, {c5, h7w, h7t, c2});
-  add("horizontal_k7_nb3", {{"MVS_NCC_MFMA7_NB", "3"}}, {c5, h7w, h7t, c2});
   add("mfma_off", {{"MVS_NCC_MFMA", "0"}}, {c2, h5n, h5t, c5, h7w, h7t});
 
   // ---- vertical and diagonal lists ----
@@ -241,7 +240,6 @@ inline std::vector<Case> cases() {
   // ---- the timing probes, on the three shapes that have one ----
   add("mfma_dbg1", {{"MVS_NCC_MFMA_DBG", "1"}, {"MVS_NCC_MFMA_V", "12"}}, {c5, c2, g33, h5n, h7t});
   add("mfma_dbg2", {{"MVS_NCC_MFMA_DBG", "2"}, {"MVS_NCC_MFMA_V", "12"}}, {c5, c2, g33, h5n, h7t});
-  add("mfma_dbg1_nb3", {{"MVS_NCC_MFMA_DBG", "1"}, {"MVS_NCC_MFMA7_NB", "3"}}, {c5});
 
   // ---- errors ----
   {
